@@ -12,6 +12,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement): metric/value/un
                  BASELINE.md section 3 in "cpu_baselines_other_configs"; "eager_rocm_baseline": the same eager ops on this GPU.
 Synthetic data of the dataset's shape (image U[0,1) (B,1,28,28), audio U[0,1) (B,1,112,112), labels randint(10),
 numpy default_rng(1234 + rank)), torch-default random init under seed 42.
+--dump-outputs DIR: after the timed steps, what the last of them computed (losses, logits, predictions, updated parameters)
+as DIR/<name>.npy, so two builds can be compared output for output (dump_outputs).
 """
 from __future__ import annotations
 
@@ -263,6 +265,34 @@ def module_path_point(cfg, B, device, precision, budget_s=4.0):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(eng, last_multi, out_dir):
+    """--dump-outputs: what the caller of the timed step holds after its last step, as out_dir/<name>.npy (float32):
+    the four losses [image, audio, fusion, total], the three heads' logits (3, B, K) and class predictions (3, B), and the
+    updated parameters (the flat fp32 master buffer, state-dict order).  Parameters beyond the size budget are replaced by
+    a fixed sample (indices drawn under seed 0, stored beside it as params_sample_index.npy, float64)."""
+    if last_multi:
+        losses, logits, preds = eng.losses_steps[-1], eng.logits_steps[-1], eng.preds_steps[-1]
+    else:
+        losses, logits, preds = eng.losses, eng.logits, eng.preds
+    arrays = {"losses": losses, "logits": logits, "preds": preds}
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    room = (DUMP_LIMIT_BYTES - sum(a.nbytes for a in arrays.values())) // 4
+    flat_p = eng.flat_p.detach().cpu().numpy()
+    if flat_p.size <= room:
+        arrays["params"] = flat_p
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(flat_p.size, size=room // 3, replace=False))
+        arrays["params_sample"] = flat_p[idx]
+        arrays["params_sample_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log(f"dumped {', '.join(arrays)} to {out_dir} ({sum(a.nbytes for a in arrays.values()) / 2**20:.1f} MB)")
+
+
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
 
@@ -329,12 +359,17 @@ def main():
     ap.add_argument("--no-module-path", action="store_true", help="skip the import-swap module-path leg (outside the timed region)")
     ap.add_argument("--cpu-budget", type=float, default=20.0)
     ap.add_argument("--profile-steps", type=int, default=10, help="eager steps with HIP events around every launch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (losses, logits, predictions, updated "
+                         "parameters) as DIR/<name>.npy, float32, at most 64 MB in all; the inputs are fixed by the seeds")
     ap.add_argument("--launch-check", action="store_true",
                     help="rendezvous only: every rank joins the process group, the ranks agree on a MAX, rank 0 prints a JSON line "
                          "(exercises the --gpus N launcher without a GPU: M2M_DIST_BACKEND=gloo)")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))             # nothing has touched the GPU yet in this process
 
@@ -431,6 +466,8 @@ def main():
     # the last step ran through the multi-step graph (its own per-step output slots) or through the single-step graph
     last_multi = multi is not None and args.steps >= spg and args.steps % spg == 0
     loss_end = float((multi.losses[-1] if last_multi else eng.losses)[3])
+    if args.dump_outputs and rank == 0:
+        dump_outputs(eng, last_multi, args.dump_outputs)         # before the profiling pass below trains further
     log(f"timed region {elapsed * 1e3:.1f} ms; profiling launches")
 
     # ---- per-launch timing (HIP events on the launch stream), eager pass of the very same step ----

@@ -314,8 +314,41 @@ def test_pipelined_grad_sync_gloo_world2():
 def test_bench_cli_contract_help():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True)
     assert r.returncode == 0
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--dump-outputs"):
         assert flag in r.stdout
+
+
+def test_bench_dump_outputs_layout_and_size_cap(tmp_path, monkeypatch):
+    """--dump-outputs writes the last step's losses / logits / predictions and the updated parameters as float32 .npy; the
+    last step of a multi-step graph is read from its own output slots; beyond the size cap the parameters become a fixed
+    sample with its indices."""
+    import types
+    import bench
+    B, K, n = 4, 10, 1000
+    eng = types.SimpleNamespace(losses=torch.zeros(4), logits=torch.zeros(3, B, K), preds=torch.zeros(3, B, dtype=torch.int32),
+                                losses_steps=torch.arange(8.0).view(2, 4), logits_steps=torch.rand(2, 3, B, K),
+                                preds_steps=torch.randint(0, K, (2, 3, B), dtype=torch.int32), flat_p=torch.rand(n))
+    bench.dump_outputs(eng, True, str(tmp_path / "a"))
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")}
+    assert sorted(got) == ["logits", "losses", "params", "preds"]
+    assert all(a.dtype == np.float32 for a in got.values())
+    assert np.array_equal(got["losses"], [4.0, 5.0, 6.0, 7.0])
+    assert np.array_equal(got["logits"], eng.logits_steps[-1].numpy())
+    assert np.array_equal(got["preds"], eng.preds_steps[-1].numpy().astype(np.float32))
+    assert np.array_equal(got["params"], eng.flat_p.numpy())
+    bench.dump_outputs(eng, False, str(tmp_path / "b"))
+    assert np.array_equal(np.load(tmp_path / "b" / "losses.npy"), np.zeros(4, np.float32))
+    cap = 4 * (4 + 3 * B * K + 3 * B) + 4 * 300
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", cap)
+    for d in ("c", "d"):
+        bench.dump_outputs(eng, False, str(tmp_path / d))
+    files = sorted(os.listdir(tmp_path / "c"))
+    assert files == ["logits.npy", "losses.npy", "params_sample.npy", "params_sample_index.npy", "preds.npy"]
+    assert sum(os.path.getsize(tmp_path / "c" / f) - 128 for f in files) <= cap
+    idx = np.load(tmp_path / "c" / "params_sample_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == 100
+    assert np.array_equal(np.load(tmp_path / "c" / "params_sample.npy"), eng.flat_p.numpy()[idx.astype(np.int64)])
+    assert np.array_equal(idx, np.load(tmp_path / "d" / "params_sample_index.npy"))
 
 
 def test_bench_gpus_n_launches_n_ranks_itself():
