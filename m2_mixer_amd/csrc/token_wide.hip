@@ -723,6 +723,14 @@ static int launch_token_fwd(const m2m_tower* t, int b, const float* src, long sr
     if (nw >= 8) return launch_token_fwd_nw<P, DM, TM, 8>(t, b, src, src_ss, B, x_mid, save_x_in, training, seed, step, step_dev, st);
     return launch_token_fwd_nw<P, DM, TM, 4>(t, b, src, src_ss, B, x_mid, save_x_in, training, seed, step, step_dev, st);
 }
+// LDS of token_bwd_cols_kernel<P, DM, TM, NW>: the prologue's tiles + per-wave gradient partials + the token-weight sums
+template <int TM, int NW>
+static size_t tok_bwd_lds_bytes(int N, int spw) {
+    constexpr int NC = TokNC<NW>::value;
+    const size_t part_f = 2 * TM * TW_COLS > 2 * NC * TW_LDW ? 2 * TM * TW_COLS : 2 * NC * TW_LDW;
+    return ((tok_lds_floats(N, spw, TM) + 3) & ~(size_t)3) * sizeof(float) +
+           ((size_t)2 * TM * TW_LDW + NW * part_f + 2 * (size_t)N * TM + TM + N) * sizeof(float);
+}
 template <int P, int DM, int TM, int NW>
 static int launch_token_bwd_nw(const m2m_tower* t, int b, const float* g_mid, int B, float* du, unsigned int seed, unsigned int step,
                             const unsigned int* step_dev, hipStream_t st) {
@@ -732,10 +740,7 @@ static int launch_token_bwd_nw(const m2m_tower* t, int b, const float* g_mid, in
     // -- the token-weight gradients end in float atomics on the same few hundred addresses from every workgroup
     const int iters = nblk > 1024 ? (nblk + 1023) / 1024 : 1;
     const int grid = (nblk + iters - 1) / iters;
-    constexpr int NC = TokNC<NW>::value;
-    const size_t part_f = 2 * TM * TW_COLS > 2 * NC * TW_LDW ? 2 * TM * TW_COLS : 2 * NC * TW_LDW;
-    const size_t lds = ((tok_lds_floats(t->N, g.spw, TM) + 3) & ~(size_t)3) * sizeof(float) +
-                       ((size_t)2 * TM * TW_LDW + NW * part_f + 2 * t->N * TM + TM + t->N) * sizeof(float);
+    const size_t lds = tok_bwd_lds_bytes<TM, NW>(t->N, g.spw);
     if (lds > 160 * 1024) { m2m_set_error("token backward: tokens x token_dim exceed the workgroup's LDS", __FILE__, __LINE__); return -1; }
     if constexpr (NW == 16 && TM <= 16) {
         if (g_ride.kind == 2 && grid <= 256) {
@@ -768,7 +773,11 @@ template <int P, int DM, int TM>
 static int launch_token_bwd(const m2m_tower* t, int b, const float* g_mid, int B, float* du, unsigned int seed, unsigned int step,
                             const unsigned int* step_dev, hipStream_t st) {
     const TokGeom g = tok_geom(t->D);
-    const int nw = tok_waves(((B + g.spw - 1) / g.spw) * g.chunks, TM);
+    int nw = tok_waves(((B + g.spw - 1) / g.spw) * g.chunks, TM);
+    // the per-wave gradient partials take 8 KiB (TM 16) / 16 KiB (TM 32) each: at large N x T fewer waves are what fits
+    // (4 waves hold every N <= 128, T <= 32)
+    if (nw == 16 && tok_bwd_lds_bytes<TM, 16>(t->N, g.spw) > 160 * 1024) nw = 8;
+    if (nw == 8 && tok_bwd_lds_bytes<TM, 8>(t->N, g.spw) > 160 * 1024) nw = 4;
     if constexpr (TM <= 16) { if (nw == 16) return launch_token_bwd_nw<P, DM, TM, 16>(t, b, g_mid, B, du, seed, step, step_dev, st); }
     if (nw >= 8) return launch_token_bwd_nw<P, DM, TM, 8>(t, b, g_mid, B, du, seed, step, step_dev, st);
     return launch_token_bwd_nw<P, DM, TM, 4>(t, b, g_mid, B, du, seed, step, step_dev, st);

@@ -700,3 +700,92 @@ def test_bf16_compressed_exchange_error_bound():
     rel_l2 = float(err.norm() / exact.norm())
     assert rel_l2 < 1e-2, rel_l2
     print(f"bf16 8-way exchange: relative L2 error {rel_l2:.2e}, max elementwise error / bound {float((err / (bound + 1e-30)).max()):.2f}")
+
+
+# ---- the shape envelope's case table (tests/shape_cases.py) against the kernel builds the library instantiates ----------------
+# The dispatch rules, restated from the C sources: m2m_is_wide (csrc/tile.h), NMAX from N (csrc/tower_fwd.hip,
+# tower_bwd.hip), TM from T (csrc/token_wide.hip M2M_TOK_DISPATCH), samples per wide token workgroup (tok_geom), the dropout
+# build from p (m2m_drop_mode / m2m_drop_thr); every case runs in both precisions.
+def _is_wide(N, D):
+    return N > 8 or D > 128
+
+
+def _drop_mode(p):
+    if p <= 0:
+        return "none"
+    thr = min(max(int((1.0 - p) * 65536.0 + 0.5), 1), 65536)
+    return "half" if thr == 32768 else "gen"
+
+
+def _builds_of(case):
+    """(path, precision, D, NMAX or TM, drop mode) of every kernel build a case reaches."""
+    out = set()
+    for prec in ("fp32", "bf16"):
+        if case.kind == "mlp":
+            out.add(("mlp", prec, None, None, "none"))
+            continue
+        dm = _drop_mode(case.p)
+        if _is_wide(case.N, case.D):
+            out.add(("wide", prec, case.D, 16 if case.T <= 16 else 32, dm))
+        else:
+            out.add(("fused", prec, case.D, 4 if case.N <= 4 else 8, dm))
+        if case.kind in ("mixer", "nopatch"):
+            out.add(("embed", prec, case.D, None, "none"))
+    return out
+
+
+def test_shape_envelope_covers_every_build():
+    from shape_cases import CASES, LDS_EDGE
+    builds = set()
+    for prec in ("fp32", "bf16"):
+        for dm in ("none", "half", "gen"):
+            builds |= {("fused", prec, D, nmax, dm) for D in (32, 64, 128) for nmax in (4, 8)}
+            builds |= {("wide", prec, D, tm, dm) for D in (32, 64, 128, 256) for tm in (16, 32)}
+        builds |= {("embed", prec, D, None, "none") for D in (32, 64, 128, 256)}
+        builds.add(("mlp", prec, None, None, "none"))
+    seen = set()
+    for c in CASES:
+        seen |= _builds_of(c)
+    missing = sorted(builds - seen, key=str)
+    assert not missing, f"kernel builds no case of tests/shape_cases.py reaches: {missing}"
+    assert seen <= builds, sorted(seen - builds, key=str)
+    assert len({c.name for c in CASES}) == len(CASES)
+
+    towers = [c for c in CASES if c.kind != "mlp"]
+    for c in towers:                                    # every case lies inside what m2m_check_tower accepts
+        assert c.D in (32, 64, 128, 256) and 1 <= c.N <= 128 and 1 <= c.T <= 32 and c.C >= 1, c.name
+        assert (c.C + 31) // 32 * 32 <= 4096 and 1 <= c.nb <= 8 and c.B >= 1, c.name
+        assert _is_wide(c.N, c.D) or c.T % 8 == 0, c.name
+    fused = [c for c in towers if not _is_wide(c.N, c.D)]
+    wide = [c for c in towers if _is_wide(c.N, c.D)]
+    assert {c.N for c in fused} == set(range(1, 9))
+    assert {32, 64, 128} <= {c.D for c in fused} and {8, 24, 32} <= {c.T for c in fused}
+    assert {1, 31, 33, 64, 100} <= {c.C for c in fused}
+    assert any(c.kind == "fusion" and (c.D, c.N, c.T, c.C, c.nb) == (LDS_EDGE["D"], LDS_EDGE["N"], LDS_EDGE["T"], LDS_EDGE["C"],
+                                                                    LDS_EDGE["nb"]) for c in fused)
+    assert {9, 16, 17, 33, 127, 128} <= {c.N for c in wide} and {1, 5, 16, 17, 31, 32} <= {c.T for c in wide}
+    assert {32, 64, 128, 256} <= {c.D for c in wide}
+    assert any(c.D == 256 and c.N <= 8 for c in wide) and any(c.C % 32 for c in wide)
+    assert any(9 <= c.N <= 23 for c in wide) and any(81 <= c.N <= 128 for c in wide)
+    # batches: B = 1, ragged against the fused tile (SPW = 16 // N samples) and, at D = 32, against the wide token
+    # workgroup's two samples (an odd B leaves the last workgroup one sample)
+    assert any(c.B == 1 for c in fused) and any(c.B == 1 for c in wide)
+    assert any(c.B % (16 // c.N) for c in fused if c.N > 1) and any(c.B > 16 for c in fused if c.N == 1)
+    assert any(c.D == 32 and c.B % 2 for c in wide)
+    # dropout: both builds on a ragged fused case and on a wide case with C not a multiple of 32
+    for dm in ("half", "gen"):
+        assert any(_drop_mode(c.p) == dm and 16 % c.N for c in fused), dm
+        assert any(_drop_mode(c.p) == dm and c.C % 32 for c in wide), dm
+    # embeddings: Cin 1 and 3, a rectangular image, K just above a k-block in both precisions, Kp at its 3968 limit,
+    # a Linear embedding whose width is not a multiple of 32
+    mix = [c for c in towers if c.kind == "mixer"]
+    ks = [c.emb[0] * c.emb[2] ** 2 for c in mix] + [c.emb for c in towers if c.kind == "nopatch"]
+    assert {1, 3} <= {c.emb[0] for c in mix} and any(c.emb[1][0] != c.emb[1][1] for c in mix)
+    assert any(k % 16 == 1 and k % 32 == 1 for k in ks) and 3968 in ks
+    assert any(c.kind == "nopatch" and c.emb % 32 for c in towers)
+    assert {32, 64, 256} <= {c.D for c in mix}
+    # the MLP: widths 1, 17 and 128; one and four Linear layers
+    mlps = [c.mlp for c in CASES if c.kind == "mlp"]
+    widths = {w for i, h, nb, o in mlps for w in (i, h, o) if w is not None}
+    layers = {nb + (o is not None) for i, h, nb, o in mlps}
+    assert {1, 17, 128} <= widths and {1, 4} <= layers
