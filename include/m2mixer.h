@@ -22,7 +22,7 @@
 extern "C" {
 #endif
 
-#define M2M_ABI_VERSION 17
+#define M2M_ABI_VERSION 18
 #define M2M_MAX_BLOCKS 8      /* MixerBlocks per m2m_tower; longer towers are chained by the caller */
 #define M2M_ROWS_PER_WG 16    /* token rows one workgroup keeps on chip */
 
@@ -328,6 +328,19 @@ int m2m_heads_ce(const m2m_head* heads, int nheads, const int64_t* labels, int B
  * pos_weight (K); per-head loss = mean over all B*K elements; preds (nheads, B, K) int32 = sigmoid(logits) > 0.5. */
 int m2m_heads_bce(const m2m_head* heads, int nheads, const float* targets, const float* pos_weight, int B, int D, int K,
                   float* logits, float* losses, int32_t* preds, int zero_losses, void* stream);
+
+/* ABI 18: m2m_heads_ce / m2m_heads_bce with the heads' loss coefficients read from DEVICE memory: weights = nheads floats (or
+ * NULL: exactly the calls above).  Non-NULL, weights[h] takes the place of heads[h].weight everywhere the kernel uses it -- the
+ * loss scale of dlogits, hence d_pooled, g_w / g_b (and g_part), and the weighted total losses[nheads].  A captured graph reads
+ * the CURRENT values on every replay, so a loss-weight schedule needs no re-capture:
+ *   m2m_heads_ce_w   models/avmnist.py:289-290 (loss = (w Lf + ow Li + ow La) * 3) with the schedule of :332-339
+ *                    (fusion_loss_weight += fusion_loss_change at each validation epoch end); models/mimic.py:115-121
+ *                    (no x3) with the schedule of :144-150;
+ *   m2m_heads_bce_w  models/mmimdb.py:115-123 (plain sum of three BCEWithLogitsLoss: coefficients 1, 1, 1). */
+int m2m_heads_ce_w(const m2m_head* heads, int nheads, const int64_t* labels, int B, int D, int K,
+                   float* logits, float* losses, int32_t* preds, int zero_losses, const float* weights, void* stream);
+int m2m_heads_bce_w(const m2m_head* heads, int nheads, const float* targets, const float* pos_weight, int B, int D, int K,
+                    float* logits, float* losses, int32_t* preds, int zero_losses, const float* weights, void* stream);
 
 /* m2m_towers_wgrad (above), which also adds the per-workgroup partial sums of the classification heads' weight gradients (m2m_head.g_part,
  * written by m2m_heads_ce at the same batch) to g_w / g_b: heads == NULL or nheads == 0: exactly m2m_towers_wgrad. */

@@ -17,6 +17,9 @@
 
 struct HeadArgs {
     m2m_head h[HEAD_MAXH];
+    // ABI 18 (m2m_heads_ce_w / m2m_heads_bce_w): the heads' loss coefficients in device memory, nheads floats, read in place of
+    // m2m_head.weight -- a captured graph then follows a loss-weight schedule (models/avmnist.py:332-339).  NULL: m2m_head.weight.
+    const float* weights;
 };
 
 // S: samples per workgroup (HEAD_S, or 4 at small batch: at the MM-IMDb cfg batch 32 samples x 3 heads were 6 workgroups).
@@ -44,6 +47,7 @@ __global__ __launch_bounds__(NTHREADS) void heads_kernel(const HeadArgs ha, cons
     const int tid = threadIdx.x;
     const int hI = blockIdx.y;
     const m2m_head& hd = ha.h[hI];
+    const float hw = ha.weights ? ha.weights[hI] : hd.weight;      // this head's coefficient in the total loss
     const int s0 = blockIdx.x * S;
     const int ns = min(S, B - s0);
 
@@ -117,7 +121,7 @@ __global__ __launch_bounds__(NTHREADS) void heads_kernel(const HeadArgs ha, cons
     // ---- loss / prediction / dlogits ----
     if (BCE) {
         // every (sample, label) element is independent -- one thread each
-        const float scale = hd.weight / ((float)B * (float)K);
+        const float scale = hw / ((float)B * (float)K);
         for (int idx = tid; idx < S * K; idx += NTHREADS) {
             const int sI = idx / K, k = idx % K;
             float term = 0.f, dl = 0.f;
@@ -159,7 +163,7 @@ __global__ __launch_bounds__(NTHREADS) void heads_kernel(const HeadArgs ha, cons
 #pragma unroll
         for (int o = 16; o >= 1; o >>= 1) se += __shfl_xor(se, o, 64);
         const int y = sI < ns ? (int)labels[s0 + sI] : 0;
-        const float scale = hd.weight / (float)B;
+        const float scale = hw / (float)B;
         const float dl = sI < ns ? scale * (ex * (1.0f / se) - (k == y ? 1.f : 0.f)) : 0.f;
         const float vy = __shfl(v, (tid & 32) + y, 64);       // the label's logit (lane y of this sample's 32 lanes)
         if (live) lg[sI * HEAD_MAXK + k] = dl;
@@ -175,7 +179,7 @@ __global__ __launch_bounds__(NTHREADS) void heads_kernel(const HeadArgs ha, cons
         for (int sI = 0; sI < S; ++sI) t += red[sI];
         t /= (float)B;
         atomicAdd(losses + hI, t);
-        atomicAdd(losses + nheads, t * hd.weight);
+        atomicAdd(losses + nheads, t * hw);
     }
     if (hd.d_pooled) {
         // d_pooled[s][d..d+3] = sum_k dl[s][k] w[k][d..d+3]: thread = (sample, float4 of d)
@@ -264,7 +268,7 @@ static int launch_heads_s(const HeadArgs& ha, int nheads, const void* labels, co
 static int heads_samples_per_wg(int B) { return B <= 64 ? 4 : HEAD_S; }
 template <bool BCE>
 static int launch_heads(const m2m_head* heads, int nheads, const void* labels, const float* pos_weight, int B, int D, int K,
-                        float* logits, float* losses, int32_t* preds, int zero_losses, void* stream) {
+                        float* logits, float* losses, int32_t* preds, int zero_losses, const float* weights, void* stream) {
     if (!heads || nheads < 1 || nheads > HEAD_MAXH || K < 2 || K > HEAD_MAXK || D < 1 || D > 256 || B < 1) {
         m2m_set_error("heads: unsupported (nheads<=4, K<=32, D<=256)", __FILE__, __LINE__);
         return -1;
@@ -282,6 +286,7 @@ static int launch_heads(const m2m_head* heads, int nheads, const void* labels, c
             return -1;
         }
     }
+    ha.weights = weights;
     for (int i = 0; i < nheads; ++i) ha.h[i] = heads[i];
     for (int i = nheads; i < HEAD_MAXH; ++i) ha.h[i] = heads[0];
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -294,11 +299,24 @@ extern "C" int m2m_heads_part_tiles(int B) { const int S = heads_samples_per_wg(
 
 extern "C" int m2m_heads_ce(const m2m_head* heads, int nheads, const int64_t* labels, int B, int D, int K, float* logits,
                             float* losses, int32_t* preds, int zero_losses, void* stream) {
-    return launch_heads<false>(heads, nheads, labels, nullptr, B, D, K, logits, losses, preds, zero_losses, stream);
+    return launch_heads<false>(heads, nheads, labels, nullptr, B, D, K, logits, losses, preds, zero_losses, nullptr, stream);
 }
 
 extern "C" int m2m_heads_bce(const m2m_head* heads, int nheads, const float* targets, const float* pos_weight, int B, int D, int K,
                              float* logits, float* losses, int32_t* preds, int zero_losses, void* stream) {
     if (!targets || !pos_weight) { m2m_set_error("heads_bce: targets and pos_weight are required", __FILE__, __LINE__); return -1; }
-    return launch_heads<true>(heads, nheads, targets, pos_weight, B, D, K, logits, losses, preds, zero_losses, stream);
+    return launch_heads<true>(heads, nheads, targets, pos_weight, B, D, K, logits, losses, preds, zero_losses, nullptr, stream);
+}
+
+// ABI 18: the same two launches with the heads' loss coefficients read from device memory (weights: nheads floats, or NULL)
+extern "C" int m2m_heads_ce_w(const m2m_head* heads, int nheads, const int64_t* labels, int B, int D, int K, float* logits,
+                              float* losses, int32_t* preds, int zero_losses, const float* weights, void* stream) {
+    return launch_heads<false>(heads, nheads, labels, nullptr, B, D, K, logits, losses, preds, zero_losses, weights, stream);
+}
+
+extern "C" int m2m_heads_bce_w(const m2m_head* heads, int nheads, const float* targets, const float* pos_weight, int B, int D,
+                               int K, float* logits, float* losses, int32_t* preds, int zero_losses, const float* weights,
+                               void* stream) {
+    if (!targets || !pos_weight) { m2m_set_error("heads_bce: targets and pos_weight are required", __FILE__, __LINE__); return -1; }
+    return launch_heads<true>(heads, nheads, targets, pos_weight, B, D, K, logits, losses, preds, zero_losses, weights, stream);
 }

@@ -166,9 +166,14 @@ class _FlatEngine:
         self.segments = bounds
         if share is not None:
             self.adam_state, self.drop_step = share.adam_state, share.drop_step
+            self.loss_weights, self._loss_weight_group = share.loss_weights, share._loss_weight_group
         else:
             self.adam_state = torch.tensor([0.0, lr, 0.0, 0.0], device=dev)     # [step, lr, -, -]
             self.drop_step = torch.zeros(1, dtype=torch.int32, device=dev)       # device-side dropout step counter
+            # the three heads' loss coefficients, read by the heads launch on every step (m2m_heads_ce_w / _bce_w): a captured
+            # graph follows set_fusion_loss_weight / set_loss_weights without being captured again
+            self.loss_weights = torch.tensor(self._head_weight_list(), dtype=torch.float32, device=dev)
+            self._loss_weight_group = {"fused_heads": False}      # (shared by the siblings, like the table itself)
         self.seed = (share.seed if share is not None else seed) & 0xFFFFFFFF
         if init and share is None:
             self.reset_parameters(seed)
@@ -190,6 +195,8 @@ class _FlatEngine:
         self.s_emb = torch.cuda.Stream(device=dev)
         self.concurrent = os.environ.get("M2M_CONCURRENT", "1") != "0"      # 0: every launch on the main stream (A/B)
         self._build()
+        if getattr(self, "_fused_heads", False):
+            self._loss_weight_group["fused_heads"] = True
         self.pack()
 
     # ---- helpers for subclasses ----------------------------------------------------------------------------
@@ -333,6 +340,31 @@ class _FlatEngine:
 
     def set_lr(self, lr: float):
         self.adam_state[1] = lr
+
+    # ---- loss weights -----------------------------------------------------------------------------------------
+    HEAD_NAMES: Tuple[str, str, str] = ("a", "b", "fusion")
+
+    def _head_weight_list(self) -> List[float]:
+        return [float(self.head_weights[n]) for n in self.HEAD_NAMES]
+
+    def set_loss_weights(self, *weights: float):
+        """The heads' coefficients in the total loss (HEAD_NAMES order: modality a, modality b, fusion), written in place into the
+        device table every heads launch reads -- this engine, its siblings and any graph captured from them use the new values
+        from their next step on.  Enqueued on the current stream (behind the steps already enqueued there)."""
+        if len(weights) != len(self.HEAD_NAMES):
+            raise ValueError(f"set_loss_weights: {len(self.HEAD_NAMES)} coefficients ({', '.join(self.HEAD_NAMES)})")
+        if self._loss_weight_group["fused_heads"]:
+            # m2m_tower_backward_heads (M2M_FUSED_HEADS=1) takes the coefficients by value: a captured graph would keep the old ones
+            raise RuntimeError("set_loss_weights: the fused heads + fusion backward launch (M2M_FUSED_HEADS=1) takes the loss "
+                               "weights by value; a changing loss weight needs that switch off")
+        vals = [float(w) for w in weights]
+        self.loss_weights.copy_(torch.tensor(vals, dtype=torch.float32))
+        self.head_weights = dict(zip(self.HEAD_NAMES, vals))
+
+    def set_fusion_loss_weight(self, w: float):
+        """The reference's `fusion_loss_weight` (the schedule of models/avmnist.py:332-339, models/mimic.py:144-150): the three
+        coefficients by this model's formula, written in place (set_loss_weights)."""
+        raise NotImplementedError(f"{type(self).__name__}: its loss has no fusion_loss_weight")
 
     def _sibling_kwargs(self) -> dict:
         return {"fusion_loss_weight": self.fusion_loss_weight} if hasattr(self, "fusion_loss_weight") else {}
@@ -516,6 +548,12 @@ class _FlatEngine:
         self._slots_folded = False
 
     # ---- hipGraph capture -----------------------------------------------------------------------------------
+    def release_capture(self):
+        """Forget the captured graph(s) (drop the replay callable too): a training sibling may then narrow the kept gradient
+        ranges (sibling()); capture() again before replaying."""
+        self._graph = None
+        self._static = None
+
     def capture(self, *batch, grad_sync=None, steps: int = 1):
         """Capture train_step on static input buffers; returns a callable replay(*batch).
         With a grad_sync the step is captured as two graphs with the all-reduce between them.
@@ -913,8 +951,16 @@ class AVMnistEngine(_TwoTowerEngine):
         self.fusion_loss_weight = w
         super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share)
 
+    HEAD_NAMES = ("image", "audio", "fusion")
+
+    def set_fusion_loss_weight(self, w: float):
+        ow = (1 - w) / 2
+        self.set_loss_weights(3 * ow, 3 * ow, 3 * w)          # loss = (w Lf + ow Li + ow La) * 3   (models/avmnist.py:289-290)
+        self.fusion_loss_weight = w
+
     def _loss_heads(self, heads, labels, zero_losses):
-        heads_ce(heads, labels, self.B, self.D, self.K, out=(self.logits, self.losses, self.preds), zero_losses=zero_losses)
+        heads_ce(heads, labels, self.B, self.D, self.K, out=(self.logits, self.losses, self.preds), zero_losses=zero_losses,
+                 weights=self.loss_weights)
 
     def _heads_are_ce(self) -> bool:
         return True
@@ -935,6 +981,7 @@ class MMIMDBEngine(_TwoTowerEngine):
     preds = sigmoid(logits) > 0.5 (:128-133); labels are (B, K) multi-hot floats."""
 
     MODS = ("image", "text")
+    HEAD_NAMES = ("image", "text", "fusion")
     #: buffers of the three BCEWithLogitsLoss modules in the reference's state_dict (models/mmimdb.py:47-50)
     EXTRA_STATE_KEYS = ("image_criterion.pos_weight", "text_criterion.pos_weight", "fusion_criterion.pos_weight")
 
@@ -964,7 +1011,7 @@ class MMIMDBEngine(_TwoTowerEngine):
 
     def _loss_heads(self, heads, labels, zero_losses):
         heads_bce(heads, labels, self.pos_weight, self.B, self.D, self.K, out=(self.logits, self.losses, self.preds),
-                  zero_losses=zero_losses)
+                  zero_losses=zero_losses, weights=self.loss_weights)
 
 
 class MimicEngine(_FlatEngine):
@@ -980,6 +1027,13 @@ class MimicEngine(_FlatEngine):
         self.head_weights = {"static": ow, "time": ow, "fusion": w}
         self.fusion_loss_weight = w
         super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share)
+
+    HEAD_NAMES = ("static", "time", "fusion")
+
+    def set_fusion_loss_weight(self, w: float):
+        ow = (1 - w) / 2
+        self.set_loss_weights(ow, ow, w)                      # loss = w Lf + ow Ls + ow Lt   (models/mimic.py:115-121, no x3)
+        self.fusion_loss_weight = w
 
     def _param_shapes(self, cfg):
         return mimic_param_shapes(cfg)
@@ -1071,7 +1125,8 @@ class MimicEngine(_FlatEngine):
         if hp:
             heads[1]["tokens"] = (time_part.data_ptr(), self.Nt, fs)
             heads[2]["tokens"] = (self.fus_out, self.Nf, fs)
-        heads_ce(heads, labels, B, D, self.K, out=(self.logits, self.losses, self.preds), zero_losses=not training)
+        heads_ce(heads, labels, B, D, self.K, out=(self.logits, self.losses, self.preds), zero_losses=not training,
+                 weights=self.loss_weights)
 
     def _backward(self, static, time, fused_update: bool = False):
         B, D = self.B, self.D

@@ -10,6 +10,10 @@ step replayed as ONE graph takes ~2 ms (bench.py: `module_path_graphed`).  What 
   re-capturing, `lr` as a device tensor: use `GraphedStep.set_lr`;
 * static input buffers: `__call__(batch)` copies the batch into them (same shapes as the example batch) and replays;
 * the warm-up steps capture needs are UNDONE (parameters, optimizer state): constructing a GraphedStep does not train.
+
+The module's `fusion_loss_weight` is a host float inside shared_step, so the graph keeps the value it was captured with: a loss-weight
+schedule (`fusion_loss_change`, validation_epoch_end) needs a new GraphedStep.  The engine-backed mode
+(`_MultiLossModule.bind_engine`) reads the loss weights from device memory and follows the schedule without re-capturing.
 """
 from __future__ import annotations
 

@@ -8,7 +8,10 @@ Same constructor contract (`model_cfg`, `optimizer_cfg` with the keys of cfg/*/*
 `.get` / attribute access), same sub-module names (hence the same state-dict keys as the published checkpoints), same
 `shared_step(batch, mode=...)` result dict, same `configure_optimizers()` (Adam + ReduceLROnPlateau on `val_loss`).
 What is NOT here is Lightning itself (trainer hooks, logging, metrics): a `pl.LightningModule` subclass can inherit from
-these and add them, or drive `to_engine()` -- the fused, hipGraph-captured step over the same weights -- from its loop.
+these and add them.  The reference's step hooks (`training_step`, `validation_step`, `test_step`, `validation_epoch_end`,
+modules/train_test_module.py:72-150) are here; after `bind_engine(batch_size)` they run the fused, hipGraph-captured step
+(engine.py) over the module's OWN parameters -- `parameters()`, `state_dict()` and checkpoints see the live weights.
+`to_engine()` is the lower-level alternative: an engine over a copy of the weights, driven by a loop of its own.
 The towers are `m2_mixer_amd.modules` (HIP kernels under torch autograd); heads and losses are the same few torch ops the
 reference uses.  SoftAdapt / GradBlend weighting are outside the scope of this build and refused loudly.
 """
@@ -90,6 +93,47 @@ def _plain(c) -> dict:
     return {k: (_plain(v) if isinstance(v, dict) else v) for k, v in dict(c).items()}
 
 
+class EngineOptimizer(torch.optim.Optimizer):
+    """The optimizer of a module bound to a fused engine (_MultiLossModule.bind_engine): the engine's Adam, which every replayed
+    training step has already applied.  step() / zero_grad() are no-ops (a LightningModule subclass sets
+    `automatic_optimization = False` when bound); `param_groups[0]["lr"]` is what schedulers such as ReduceLROnPlateau write --
+    the next training_step pushes a changed value to the engine (engine.set_lr); state_dict() / load_state_dict() are the
+    engine's Adam state in torch.optim.Adam's layout (a plain Adam over the same parameters loads it, and vice versa)."""
+
+    def __init__(self, engine, params):
+        lr = float(engine.adam_state[1])
+        super().__init__(params, dict(lr=lr, betas=tuple(engine.betas), eps=engine.eps, weight_decay=engine.weight_decay,
+                                      amsgrad=False, maximize=False))
+        self.engine = engine
+        self._pushed_lr = lr
+
+    def sync_lr(self) -> None:
+        """Push a learning rate a scheduler wrote into param_groups to the engine (host floats compared: no sync)."""
+        lr = self.param_groups[0]["lr"]
+        if lr != self._pushed_lr:
+            self.engine.set_lr(float(lr))
+            self._pushed_lr = lr
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        return closure() if closure is not None else None
+
+    def zero_grad(self, set_to_none: bool = True) -> None:
+        pass
+
+    def state_dict(self) -> dict:
+        self.sync_lr()
+        return self.engine.optimizer_state_dict()
+
+    def load_state_dict(self, state_dict: dict) -> None:
+        self.engine.load_optimizer_state_dict(state_dict)
+        if state_dict.get("param_groups"):
+            lr = state_dict["param_groups"][0]["lr"]
+            for g in self.param_groups:
+                g["lr"] = lr
+            self._pushed_lr = lr
+
+
 class _MultiLossModule(nn.Module):
     MODS: Tuple[str, str] = ("a", "b")
 
@@ -106,9 +150,14 @@ class _MultiLossModule(nn.Module):
         self.random_modality_muting_on_freeze = self.model_cfg.get("random_modality_muting_on_freeze", False)
         self.muting_probs = self.model_cfg.get("muting_probs", None)
         self.fusion_loss_weight = self.model_cfg.get("fusion_loss_weight", 1.0 / 3)
+        # the loss-weight schedule of validation_epoch_end (models/avmnist.py:197-198, :338-339; models/mimic.py:54-55, :149-150)
+        self.fusion_loss_change = self.model_cfg.get("fusion_loss_change", 0)
+        self.loss_change_epoch = self.model_cfg.get("loss_change_epoch", 0)
         self.modalities_freezed = False
         self.current_epoch = 0                       # a trainer sets it (Lightning property in the reference)
         self.dropout = self.model_cfg.get("dropout", 0.0)
+        self._engine = None                          # bind_engine: the fused engine whose buffers hold this module's parameters
+        self._engine_optimizer: Optional[EngineOptimizer] = None     # the latest configure_optimizers() of a bound module
 
     # ---- pieces shared by the three tasks ----------------------------------------------------------------
     def _fusion_and_heads(self, n_a: int, n_b: int, dim_a: int, dim_b: int):
@@ -176,6 +225,10 @@ class _MultiLossModule(nn.Module):
         sd = {k: v.detach().cpu() for k, v in self.state_dict().items()}
         ckpt = {"state_dict": sd, "epoch": self.current_epoch if epoch is None else int(epoch), "global_step": int(global_step),
                 "pytorch-lightning_version": LIGHTNING_VERSION, "optimizer_states": [], "lr_schedulers": []}
+        if engine is None and self._engine is not None:
+            engine = self._engine                    # bound: the optimizer state is the engine's
+            if self._engine_optimizer is not None:
+                self._engine_optimizer.sync_lr()
         if engine is not None:
             for k, v in engine.state_dict().items():
                 sd[k] = v.detach().cpu()
@@ -200,9 +253,13 @@ class _MultiLossModule(nn.Module):
         return path
 
     def configure_optimizers(self) -> Dict[str, Any]:
-        """models/avmnist.py:413-422."""
+        """models/avmnist.py:413-422.  Bound to an engine (bind_engine): the optimizer is an EngineOptimizer -- the engine's
+        fused Adam, which every training_step already applies; ReduceLROnPlateau drives its learning rate as usual."""
         from torch.optim.lr_scheduler import ReduceLROnPlateau
-        optimizer = torch.optim.Adam(filter(lambda p: p.requires_grad, self.parameters()), **self.optimizer_cfg)
+        if self._engine is not None:
+            optimizer = self._engine_optimizer = EngineOptimizer(self._engine, list(self.parameters()))
+        else:
+            optimizer = torch.optim.Adam(filter(lambda p: p.requires_grad, self.parameters()), **self.optimizer_cfg)
         return {"optimizer": optimizer, "lr_scheduler": ReduceLROnPlateau(optimizer, patience=self.scheduler_patience),
                 "monitor": "val_loss"}
 
@@ -223,6 +280,186 @@ class _MultiLossModule(nn.Module):
         eng = self._make_engine(self._engine_cfg(), batch_size, next(self.parameters()).device, precision)
         eng.load_state_dict(self.state_dict())
         return eng
+
+    # ---- engine-backed mode ----------------------------------------------------------------------------------
+    @property
+    def engine(self):
+        """The fused engine this module is bound to (bind_engine), or None."""
+        return self._engine
+
+    def bind_engine(self, batch_size: int, precision: Optional[str] = None):
+        """Engine-backed mode: build the fused engine (engine.py) for `batch_size`, copy this module's weights into it, then
+        point every parameter's `.data` at the engine's buffer (`engine.params[key]`): the Parameter objects stay the same,
+        `parameters()`, `state_dict()`, `save_checkpoint()` read the live weights, and no copy is taken again.  From then on
+        training_step replays the engine's captured step, validation_step / test_step run its evaluation, configure_optimizers
+        returns an EngineOptimizer and validation_epoch_end forwards the loss-weight schedule to the engine.
+        A LightningModule subclass sets `automatic_optimization = False` when bound: the replayed step already updated the
+        weights (EngineOptimizer.step is a no-op).  Refused: epoch-triggered freezing and random muting (the engine trains every
+        parameter and has no muting); a fixed `mute` is supported."""
+        if self._engine is not None:
+            raise RuntimeError("bind_engine: this module is already bound to an engine")
+        if self.freeze_modalities_on_epoch is not None or self.modalities_freezed:
+            raise NotImplementedError("bind_engine: freeze_modalities_on_epoch -- the fused engine trains every parameter")
+        if self.random_modality_muting_on_freeze:
+            raise NotImplementedError("bind_engine: random_modality_muting_on_freeze -- the fused engine has no random muting")
+        dev = next(self.parameters()).device
+        if dev.type != "cuda":
+            raise RuntimeError("bind_engine: the module must be on the GPU (.to('cuda')) first; the engine has no CPU path")
+        eng = self._make_engine(self._engine_cfg(), batch_size, dev, precision)
+        eng.load_state_dict(self.state_dict())
+        with torch.no_grad():
+            for k, p in self.named_parameters():
+                p.data = eng.params[k]
+        self._bind_buffers(eng)
+        self._engine = eng
+        self._replay = None
+        self._train_siblings: Dict[int, Any] = {}
+        self._eval_siblings: Dict[int, Any] = {}
+        self._engine_version = 0                     # += 1 whenever the weights change (an engine step, a load_state_dict)
+        self._hip_modules = [m for m in self.modules() if hasattr(m, "invalidate_packs")]
+        self._invalidate_module_packs()
+        return eng
+
+    def _bind_buffers(self, eng):
+        """Loss-module buffers that live in the engine (MM-IMDb's pos_weight)."""
+
+    def _invalidate_module_packs(self):
+        # the engine updates the weights without advancing autograd's version counters: the module's own tower / embedding
+        # runtimes would keep their packed copies; a later shared_step / forward re-packs
+        for m in self._hip_modules:
+            m.invalidate_packs()
+
+    def load_state_dict(self, state_dict, strict: bool = True, assign: bool = False):
+        if self._engine is None:
+            return super().load_state_dict(state_dict, strict=strict, assign=assign)
+        if assign:
+            raise RuntimeError("load_state_dict(assign=True) would detach the parameters from the bound engine")
+        self._check_engine_state(state_dict)
+        res = super().load_state_dict(state_dict, strict=strict)       # writes into the engine's buffers (the parameters' views)
+        self._engine.pack()
+        self._engine_version += 1
+        self._invalidate_module_packs()
+        return res
+
+    def _check_engine_state(self, state_dict):
+        pass
+
+    def _engine_batch(self, batch, train: bool) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(input a, input b, labels) in the engine's layout, with shared_step's fixed muting in train mode."""
+        raise NotImplementedError
+
+    def _two_tower_batch(self, batch, train: bool, labels):
+        a, b = self.MODS
+        xa, xb = batch[a], batch[b]
+        if train and self.mute == a:                 # shared_step's fixed muting (train mode only)
+            xa = torch.zeros_like(xa)
+        elif train and self.mute == b:
+            xb = torch.zeros_like(xb)
+        return xa.float(), xb.float(), labels
+
+    def _engine_train_outputs(self, eng, labels) -> Dict[str, torch.Tensor]:
+        a, b = self.MODS
+        l = eng.losses.clone()
+        return {"loss": l[3], f"loss_{a}": l[0], f"loss_{b}": l[1], "loss_fusion": l[2], "preds": self._engine_preds(eng.preds[2], eng.logits[2]),
+                "labels": labels}
+
+    def _engine_preds(self, preds, logits) -> torch.Tensor:
+        """shared_step's `preds` from the engine's (int32 decisions, logits) of one head -- a new tensor."""
+        return preds.long()
+
+    def _engine_eval_outputs(self, eng, batch, labels) -> Dict[str, torch.Tensor]:
+        """shared_step(mode="val") of the two-tower models: same keys, same meanings."""
+        a, b = self.MODS
+        l, lg, pr = eng.losses.clone(), eng.logits.clone(), eng.preds.long()
+        return {"preds": pr[2], f"preds_{a}": pr[0], f"preds_{b}": pr[1], "labels": batch["label"], "loss": l[3],
+                f"loss_{a}": l[0], f"loss_{b}": l[1], "loss_fusion": l[2], f"{a}_logits": lg[0], f"{b}_logits": lg[1],
+                "logits": lg[2]}
+
+    def _train_sibling(self, bs: int):
+        sib = self._train_siblings.get(bs)
+        if sib is None:
+            if self._replay is not None:
+                # sibling() may narrow the gradient ranges the captured update leaves uncleared: capture again afterwards
+                self._replay = None
+                self._engine.release_capture()
+            sib = self._train_siblings[bs] = self._engine.sibling(bs)
+            self._link_sibling(sib)
+        return sib
+
+    def _eval_sibling(self, bs: int):
+        sib = self._eval_siblings.get(bs)
+        if sib is None:
+            sib = self._eval_siblings[bs] = self._engine.sibling(bs, trains=False)
+            self._link_sibling(sib)
+            sib._bound_version = -1
+        if sib._bound_version != self._engine_version:
+            sib.pack()                               # its packed copies missed the steps since its last use
+            sib._bound_version = self._engine_version
+        return sib
+
+    def _link_sibling(self, sib):
+        pass
+
+    def training_step(self, batch, batch_idx: int = 0) -> Dict[str, torch.Tensor]:
+        """modules/train_test_module.py:72-84.  Unbound: shared_step(batch, mode="train").  Bound: one fused training step --
+        the captured graph for full batches (captured on the first one), a training sibling for any other batch size (the
+        ragged last batch of an epoch).  Returns the loss keys of shared_step, `preds` and `labels`: device tensors CLONED out
+        of the engine's buffers (the next replay overwrites those); nothing synchronises with the host."""
+        eng = self._engine
+        if eng is None:
+            return self.shared_step(batch, mode="train")
+        if self.modalities_freezed:
+            raise NotImplementedError("a bound module trains every parameter: freezing is not supported")
+        xa, xb, labels = self._engine_batch(batch, train=True)
+        if self._engine_optimizer is not None:
+            self._engine_optimizer.sync_lr()         # ReduceLROnPlateau's cut (host floats compared: no sync)
+        bs = labels.shape[0]
+        if bs == eng.B:
+            if self._replay is None:
+                self._replay = eng.capture(xa, xb, labels)
+            self._replay(xa, xb, labels)
+            src = eng
+        else:
+            src = self._train_sibling(bs)
+            src.pack()                               # pack-before / pack-after (data.run_epoch)
+            src.train_step(xa.contiguous(), xb.contiguous(), labels.contiguous())
+            eng.pack()
+        self._engine_version += 1
+        self._invalidate_module_packs()
+        return self._engine_train_outputs(src, labels)
+
+    def _eval_step(self, batch, mode: str) -> Dict[str, torch.Tensor]:
+        if self._engine is None:
+            return self.shared_step(batch, mode=mode)
+        xa, xb, labels = self._engine_batch(batch, train=False)
+        sib = self._eval_sibling(labels.shape[0])
+        sib.evaluate(xa.contiguous(), xb.contiguous(), labels.contiguous())
+        return self._engine_eval_outputs(sib, batch, labels)
+
+    def validation_step(self, batch, batch_idx: int = 0) -> Dict[str, torch.Tensor]:
+        """modules/train_test_module.py:94-104.  Bound: the engine's evaluation (dropout off) through an evaluating sibling per
+        batch size; the keys and meanings of shared_step(mode="val"), as cloned device tensors."""
+        return self._eval_step(batch, "val")
+
+    def test_step(self, batch, batch_idx: int = 0) -> Dict[str, torch.Tensor]:
+        """modules/train_test_module.py:132-142 (see validation_step); save_test_preds takes a list of these."""
+        return self._eval_step(batch, "test")
+
+    #: whether validation_epoch_end applies the fusion-loss-weight schedule (the reference's AV-MNIST and MIMIC models do)
+    LOSS_SCHEDULE = True
+
+    def validation_epoch_end(self, outputs=None) -> None:
+        """The loss-weight schedule of models/avmnist.py:338-339 / models/mimic.py:149-150: from epoch `loss_change_epoch` on,
+        fusion_loss_weight grows by `fusion_loss_change` per validation epoch, up to 1.  Bound: forwarded to the engine, whose
+        captured step reads the new coefficients on its next replay.  (The reference's logging part is Lightning's.)"""
+        if not self.LOSS_SCHEDULE or self.current_epoch < self.loss_change_epoch:
+            return
+        new = min(1, self.fusion_loss_weight + self.fusion_loss_change)
+        if new == self.fusion_loss_weight:
+            return
+        if self._engine is not None:
+            self._engine.set_fusion_loss_weight(float(new))
+        self.fusion_loss_weight = new
 
 
 class AVMnistMixerMultiLoss(_MultiLossModule):
@@ -266,6 +503,9 @@ class AVMnistMixerMultiLoss(_MultiLossModule):
                 "loss_audio": loss_audio, "loss_fusion": loss_fusion, "image_logits": image_logits,
                 "audio_logits": audio_logits, "logits": logits}
 
+    def _engine_batch(self, batch, train):
+        return self._two_tower_batch(batch, train, batch["label"].long())
+
     def _make_engine(self, cfg, batch_size, device, precision):
         from .engine import AVMnistEngine
         return AVMnistEngine(cfg, batch_size, device=device, precision=precision,
@@ -278,6 +518,7 @@ class MMIMDBMixerMultiLoss(_MultiLossModule):
     MODS = ("image", "text")
 
     TEST_PRED_KEYS = ("preds", "preds_image", "preds_text", "labels", "image_logits", "text_logits", "logits")   # models/mmimdb.py:194-209
+    LOSS_SCHEDULE = False                            # a plain sum of the three losses (models/mmimdb.py:115-123): no schedule
 
     def __init__(self, model_cfg, optimizer_cfg, **kwargs):
         super().__init__(model_cfg, optimizer_cfg, **kwargs)
@@ -324,6 +565,23 @@ class MMIMDBMixerMultiLoss(_MultiLossModule):
         cfg["pos_weight"] = pw[0].detach().cpu().tolist()          # the loaded buffers, not the cfg: a checkpoint may carry its own
         return cfg
 
+    def _engine_batch(self, batch, train):
+        return self._two_tower_batch(batch, train, batch["label"].float())
+
+    def _bind_buffers(self, eng):
+        # the three criteria's pos_weight buffers ARE the engine's (one tensor: the fused heads take one pos_weight)
+        for c in (self.image_criterion, self.text_criterion, self.fusion_criterion):
+            c.pos_weight = eng.pos_weight
+
+    def _link_sibling(self, sib):
+        sib.pos_weight = self._engine.pos_weight
+
+    def _check_engine_state(self, state_dict):
+        keys = [f"{n}_criterion.pos_weight" for n in ("image", "text", "fusion")]
+        pw = [state_dict[k] for k in keys if k in state_dict]
+        if any(not torch.equal(pw[0].cpu(), p.cpu()) for p in pw[1:]):
+            raise RuntimeError("the bound engine takes one pos_weight for all three heads (models/mmimdb.py:47-50 builds them equal)")
+
     def _make_engine(self, cfg, batch_size, device, precision):
         from .engine import MMIMDBEngine
         return MMIMDBEngine(cfg, batch_size, device=device, precision=precision, init=False, **self._engine_kwargs())
@@ -359,6 +617,20 @@ class MimicMixerMultiLoss(_MultiLossModule):
                 "preds_time": torch.softmax(logits_time, dim=1), "labels": labels.long(), "loss": loss,
                 "loss_fusion": loss_fusion, "loss_static": loss_static, "loss_time": loss_time, "logits": logits,
                 "logits_static": logits_static, "logits_time": logits_time}
+
+    def _engine_batch(self, batch, train):
+        static, time, labels = batch
+        return static.float(), time.float(), labels.long()
+
+    def _engine_preds(self, preds, logits):
+        return torch.softmax(logits, dim=1)         # shared_step's `preds` are the fusion head's probabilities (models/mimic.py:126)
+
+    def _engine_eval_outputs(self, eng, batch, labels):
+        l, lg = eng.losses.clone(), eng.logits.clone()
+        p = torch.softmax(lg, dim=2)
+        return {"preds": p[2], "preds_static": p[0], "preds_time": p[1], "labels": labels, "loss": l[3],
+                "loss_fusion": l[2], "loss_static": l[0], "loss_time": l[1], "logits": lg[2], "logits_static": lg[0],
+                "logits_time": lg[1]}
 
     def _make_engine(self, cfg, batch_size, device, precision):
         from .engine import MimicEngine

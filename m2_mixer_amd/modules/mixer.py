@@ -161,6 +161,15 @@ class _HipTower(nn.Module):
         self._drop_step += 1                 # (host mirror: exact in eager mode; replays advance only the device counter)
         return 0, ctr
 
+    def invalidate_packs(self):
+        """The weights changed behind autograd's version counters (a fused engine trains them in place:
+        models._MultiLossModule.bind_engine): the next forward rebuilds the packed operand copies."""
+        for rt in self._rts or ():
+            rt.invalidate()
+        ert = getattr(self, "_ert", None)
+        if ert is not None:
+            ert.invalidate()
+
     def _tower_blocks(self) -> List["MixerBlock"]:
         raise NotImplementedError
 

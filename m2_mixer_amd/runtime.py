@@ -580,6 +580,10 @@ class EmbedRuntime:
     def mark_packed(self):
         self._packed_for = self._keep["w"]._version
 
+    def invalidate(self):
+        """As TowerRuntime.invalidate: the next pack() rebuilds the packed copy."""
+        self._packed_for = None
+
     def pack(self, force: bool = False):
         if force or self._keep["w"]._version != self._packed_for:
             L.check(L.lib().m2m_pack_embed(C.byref(self.desc), L.stream_ptr()), "pack_embed")
@@ -738,11 +742,20 @@ def _head_array(heads: Sequence[dict]):
     return arr
 
 
+def _check_weights(weights: Optional[torch.Tensor], nh: int):
+    if weights is not None and (not weights.is_cuda or weights.dtype != torch.float32 or weights.numel() < nh
+                                or not weights.is_contiguous()):
+        raise ValueError(f"head weights: a contiguous float32 device tensor of at least {nh} entries")
+
+
 def heads_bce(heads: Sequence[dict], targets: torch.Tensor, pos_weight: torch.Tensor, B: int, D: int, K: int, out=None,
-              zero_losses: bool = True):
+              zero_losses: bool = True, weights: Optional[torch.Tensor] = None):
     """BCEWithLogitsLoss(pos_weight) heads (models/mmimdb.py:47-50): targets (B, K) float32 multi-hot.
-    Returns logits (nh, B, K), losses (nh + 1), preds (nh, B, K) int32."""
+    Returns logits (nh, B, K), losses (nh + 1), preds (nh, B, K) int32.
+    weights: the heads' loss coefficients as a device tensor (m2m_heads_bce_w: read on every launch, so a captured graph follows
+    changes to it); None: each head's `weight` (m2m_heads_bce)."""
     nh = len(heads)
+    _check_weights(weights, nh)
     arr = _head_array(heads)
     _check_tensor(targets, (B, K), "BCE targets")
     dev = targets.device
@@ -752,15 +765,23 @@ def heads_bce(heads: Sequence[dict], targets: torch.Tensor, pos_weight: torch.Te
         logits = torch.empty(nh, B, K, device=dev)
         losses = torch.empty(nh + 1, device=dev)
         preds = torch.empty(nh, B, K, dtype=torch.int32, device=dev)
-    L.check(L.lib().m2m_heads_bce(arr, nh, targets.data_ptr(), pos_weight.data_ptr(), B, D, K, logits.data_ptr(),
-                                  losses.data_ptr(), preds.data_ptr(), int(zero_losses), L.stream_ptr()), "heads_bce")
+    if weights is not None:
+        L.check(L.lib().m2m_heads_bce_w(arr, nh, targets.data_ptr(), pos_weight.data_ptr(), B, D, K, logits.data_ptr(),
+                                        losses.data_ptr(), preds.data_ptr(), int(zero_losses), weights.data_ptr(), L.stream_ptr()),
+                "heads_bce_w")
+    else:
+        L.check(L.lib().m2m_heads_bce(arr, nh, targets.data_ptr(), pos_weight.data_ptr(), B, D, K, logits.data_ptr(),
+                                      losses.data_ptr(), preds.data_ptr(), int(zero_losses), L.stream_ptr()), "heads_bce")
     return logits, losses, preds
 
 
-def heads_ce(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: int, out=None, zero_losses: bool = True):
+def heads_ce(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: int, out=None, zero_losses: bool = True,
+             weights: Optional[torch.Tensor] = None):
     """heads: dicts with pooled, w, b, g_w, g_b, d_pooled (tensors or None) and weight.
-    Returns logits (nh, B, K), losses (nh + 1), preds (nh, B) int32 (written into `out` if given)."""
+    Returns logits (nh, B, K), losses (nh + 1), preds (nh, B) int32 (written into `out` if given).
+    weights: the heads' loss coefficients as a device tensor (m2m_heads_ce_w), None: each head's `weight`."""
     nh = len(heads)
+    _check_weights(weights, nh)
     arr = _head_array(heads)
     dev = labels.device
     if out is not None:
@@ -769,6 +790,10 @@ def heads_ce(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: int
         logits = torch.empty(nh, B, K, device=dev)
         losses = torch.empty(nh + 1, device=dev)
         preds = torch.empty(nh, B, dtype=torch.int32, device=dev)
-    L.check(L.lib().m2m_heads_ce(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(),
-                                 preds.data_ptr(), int(zero_losses), L.stream_ptr()), "heads_ce")
+    if weights is not None:
+        L.check(L.lib().m2m_heads_ce_w(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(),
+                                       preds.data_ptr(), int(zero_losses), weights.data_ptr(), L.stream_ptr()), "heads_ce_w")
+    else:
+        L.check(L.lib().m2m_heads_ce(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(),
+                                     preds.data_ptr(), int(zero_losses), L.stream_ptr()), "heads_ce")
     return logits, losses, preds
