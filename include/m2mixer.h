@@ -464,6 +464,36 @@ int m2m_step_prologue(float* adam_state, uint32_t* drop_counter, float* losses, 
 /* *counter += delta on the stream (device uint32). */
 int m2m_counter_add(uint32_t* counter, uint32_t delta, void* stream);
 
+/* ---- fusion functions other than ConcatFusion (additive within ABI 18) ------------------------------------------------
+ * SumFusion / MeanFusion / MaxFusion (modules/fusion.py:190-221, :258-272) on n floats (n a multiple of 4, 16-byte aligned
+ * buffers): y = a + b, (a + b) / 2, max(a, b).  The backward writes d_a and d_b; max follows torch.maximum: on a tie each
+ * input takes half of the gradient. */
+#define M2M_FUSION_SUM 1
+#define M2M_FUSION_MEAN 2
+#define M2M_FUSION_MAX 3
+int m2m_fusion_forward(int mode, const float* a, const float* b, float* y, int64_t n, void* stream);
+int m2m_fusion_backward(int mode, const float* a, const float* b, const float* dy, float* da, float* db, int64_t n, void* stream);
+
+/* BiModalGatedUnit (modules/fusion.py:7-55) on (rows, D) row-major fp32 tensors, D in {32, 64, 128, 256}:
+ *   y = z * tanh(W1 a + b1) + (1 - z) * tanh(W2 b + b2),   z = sigmoid(Wz [a, b] + bz)
+ * in exact fp32, with the weights read from the fp32 masters (mod1_hidden, mod2_hidden, z_hidden: (D, D), (D, D), (D, 2D)).
+ * A training forward (save = 1) keeps t1 = tanh(W1 a + b1), t2, z in the (rows, D) buffers t1 / t2 / z; the backward reads
+ * them, writes d_a, d_b and the pre-activation gradients into dh ((rows, 3 D)); the weight-gradient call then ADDS the six
+ * parameter gradients into g_* (per-workgroup partial sums in `part`, m2m_gate_part_floats(rows, D) floats, added in a fixed
+ * order: no float atomics).  Parameters and their gradients 4-byte aligned (views of a flat buffer), every other buffer 16-byte
+ * aligned. */
+typedef struct m2m_gate {
+    int32_t D;
+    int32_t reserved;
+    const float *w1, *b1, *w2, *b2, *wz, *bz;
+    float *g_w1, *g_b1, *g_w2, *g_b2, *g_wz, *g_bz;
+    float *t1, *t2, *z, *dh, *part;
+} m2m_gate;
+int64_t m2m_gate_part_floats(int64_t rows, int D);
+int m2m_gate_forward(const m2m_gate* g, const float* a, const float* b, float* y, int64_t rows, int save, void* stream);
+int m2m_gate_backward(const m2m_gate* g, const float* dy, float* da, float* db, int64_t rows, void* stream);
+int m2m_gate_wgrad(const m2m_gate* g, const float* a, const float* b, int64_t rows, void* stream);
+
 /* ---- test hooks ----------------------------------------------------------------------------------- */
 /* keep-mask (uint8, 1 keep) the kernels use for dropout site `site` (0 tok hidden, 1 tok out,
  * 2 channel hidden, 3 channel out) of block `blk` of tower t at (seed, step): rows x cols elements with

@@ -96,6 +96,15 @@ class Head(C.Structure):
                 ("weight", C.c_float), ("g_part", _fp), ("tokens", _fp), ("tok_sample_stride", C.c_int64), ("ntok", C.c_int32)]
 
 
+FUSION_SUM, FUSION_MEAN, FUSION_MAX = 1, 2, 3      # m2m_fusion_forward / _backward modes (M2M_FUSION_*)
+
+
+class Gate(C.Structure):
+    """m2m_gate"""
+    _fields_ = [("D", C.c_int32), ("reserved", C.c_int32)] + [(n, _fp) for n in (
+        "w1", "b1", "w2", "b2", "wz", "bz", "g_w1", "g_b1", "g_w2", "g_b2", "g_wz", "g_bz", "t1", "t2", "z", "dh", "part")]
+
+
 MLP_MAX_LAYERS = 4
 
 
@@ -163,6 +172,13 @@ SIGNATURES = {
     # ABI 18: the heads' loss coefficients from device memory (the argument before the stream; NULL: m2m_head.weight)
     "m2m_heads_ce_w": (C.c_int, [C.POINTER(Head), C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, _fp, _fp]),
     "m2m_heads_bce_w": (C.c_int, [C.POINTER(Head), C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, _fp, _fp]),
+    # fusion functions other than ConcatFusion (csrc/fusion.hip)
+    "m2m_fusion_forward": (C.c_int, [C.c_int, _fp, _fp, _fp, C.c_int64, _fp]),
+    "m2m_fusion_backward": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_int64, _fp]),
+    "m2m_gate_part_floats": (C.c_int64, [C.c_int64, C.c_int]),
+    "m2m_gate_forward": (C.c_int, [C.POINTER(Gate), _fp, _fp, _fp, C.c_int64, C.c_int, _fp]),
+    "m2m_gate_backward": (C.c_int, [C.POINTER(Gate), _fp, _fp, _fp, C.c_int64, _fp]),
+    "m2m_gate_wgrad": (C.c_int, [C.POINTER(Gate), _fp, _fp, C.c_int64, _fp]),
     "m2m_mlp_forward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, C.c_int, C.c_uint32, C.c_uint32,
                                   _fp, _fp]),
     "m2m_mlp_backward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, _fp]),

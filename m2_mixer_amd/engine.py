@@ -20,6 +20,7 @@ from __future__ import annotations
 from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
+import ctypes as C
 import os
 
 import torch
@@ -71,14 +72,48 @@ def _head_shapes(s, names: Sequence[str], dims: Sequence[int], K: int):
         s[key + "bias"] = (K,)
 
 
+#: fusion functions (cfg["multimodal"]["fusion_function"]) the two-tower engines build; ConcatFusion when the key is absent
+ENGINE_FUSIONS = ("ConcatFusion", "SumFusion", "MeanFusion", "MaxFusion", "BiModalGatedUnit")
+_ELEM_FUSION_MODE = {"SumFusion": L.FUSION_SUM, "MeanFusion": L.FUSION_MEAN, "MaxFusion": L.FUSION_MAX}
+
+
+def fusion_function_name(mm: dict) -> str:
+    """cfg["multimodal"]'s fusion function; refuses the ones the engines do not build (ConcatDynaFusion, ExtraConcatFusion)."""
+    name = mm.get("fusion_function", "ConcatFusion")
+    if name not in ENGINE_FUSIONS:
+        raise RuntimeError(f"multimodal.fusion_function = {name!r}: the fused engines build {', '.join(ENGINE_FUSIONS)}")
+    return name
+
+
+def fusion_tokens(mm: dict, na: int, nb: int) -> int:
+    """Tokens of the fusion tower: the registry's own get_output_shape(na, nb, dim=1) (models/avmnist.py:183-186), so unequal
+    token counts are refused as the reference refuses them (sum / mean / max: ValueError)."""
+    from .modules import fusion as F
+    name = fusion_function_name(mm)
+    if name == "BiModalGatedUnit":
+        if na != nb:       # (its get_output_shape does not check; the reference fails inside torch.cat)
+            raise RuntimeError(f"multimodal.fusion_function = BiModalGatedUnit needs equal token counts, got {na} and {nb}")
+        return na
+    fn = F.ConcatFusion(dim=1) if name == "ConcatFusion" else getattr(F, name)()
+    return int(fn.get_output_shape(na, nb, dim=1))
+
+
 def two_tower_param_shapes(cfg: dict, mods: Tuple[str, str]) -> "OrderedDict[str, tuple]":
-    """state-dict key -> shape in the reference's creation order (models/avmnist.py:181-191, models/mmimdb.py:35-45)."""
+    """state-dict key -> shape in the reference's creation order (models/avmnist.py:181-191, models/mmimdb.py:35-45): the two
+    towers, the fusion function's parameters (BiModalGatedUnit only), the fusion mixer, the three heads."""
     s: "OrderedDict[str, tuple]" = OrderedDict()
     a, b = mods
+    mm = cfg["multimodal"]
     na, nb = _num_patch(cfg[a]), _num_patch(cfg[b])
+    nf = fusion_tokens(mm, na, nb)
     _tower_shapes(s, f"{a}_mixer.", cfg[a], na, "patch")
     _tower_shapes(s, f"{b}_mixer.", cfg[b], nb, "patch")
-    _tower_shapes(s, "fusion_mixer.", cfg["multimodal"], na + nb, None)
+    if fusion_function_name(mm) == "BiModalGatedUnit":
+        i1, i2, o = mm["mod1_in"], mm["mod2_in"], mm["out_size"]
+        for k, fan_in in (("mod1_hidden", i1), ("mod2_hidden", i2), ("z_hidden", i1 + i2)):       # modules/fusion.py:10-14
+            s[f"fusion_function.{k}.weight"] = (o, fan_in)
+            s[f"fusion_function.{k}.bias"] = (o,)
+    _tower_shapes(s, "fusion_mixer.", mm, nf, None)
     _head_shapes(s, (a, b, "fusion"), (cfg[a]["hidden_dim"], cfg[b]["hidden_dim"], cfg["multimodal"]["hidden_dim"]),
                  cfg["num_classes"])
     return s
@@ -661,7 +696,10 @@ class _FlatEngine:
 
 
 class _TwoTowerEngine(_FlatEngine):
-    """Two MLPMixer towers (patch embedding) -> ConcatFusion(dim=1) -> FusionMixer -> three heads."""
+    """Two MLPMixer towers (patch embedding) -> fusion function -> FusionMixer -> three heads.
+    ConcatFusion(dim=1) (the default) costs nothing: the towers write the halves of the fusion tower's input.  Sum / mean / max
+    and BiModalGatedUnit: the towers write buffers of their own, one launch fuses them (m2m_fusion_forward / m2m_gate_forward)
+    and its backward splits the fusion tower's input gradient (the gate adds a weight-gradient launch)."""
 
     MODS: Tuple[str, str] = ("image", "audio")
 
@@ -677,10 +715,15 @@ class _TwoTowerEngine(_FlatEngine):
         cfg = self.cfg
         ca, cb, cm = cfg[a], cfg[b], cfg["multimodal"]
         self.D = ca["hidden_dim"]
+        self.fusion_name = fusion_function_name(cm)
+        self.concat = self.fusion_name == "ConcatFusion"
         if not (cb["hidden_dim"] == self.D == cm["hidden_dim"]):
-            raise RuntimeError("both towers and the fusion mixer must share hidden_dim (ConcatFusion on dim 1)")
+            raise RuntimeError(f"both towers and the fusion mixer must share hidden_dim ({self.fusion_name} on dim 1)")
+        if self.fusion_name == "BiModalGatedUnit" and not (cm["mod1_in"] == cm["mod2_in"] == cm["out_size"] == self.D):
+            raise RuntimeError(f"multimodal.mod1_in / mod2_in / out_size = {cm['mod1_in']} / {cm['mod2_in']} / {cm['out_size']}: "
+                               f"the engine's BiModalGatedUnit takes and gives the towers' hidden_dim {self.D} (one D for the heads)")
         self.Na, self.Nb = _num_patch(ca), _num_patch(cb)
-        self.Nf = self.Na + self.Nb
+        self.Nf = fusion_tokens(cm, self.Na, self.Nb)
         self.t_a = self._make_tower(f"{a}_mixer.", ca, self.Na, 0)
         self.t_b = self._make_tower(f"{b}_mixer.", cb, self.Nb, 1024)
         self.t_fus = self._make_tower("fusion_mixer.", cm, self.Nf, 2048)
@@ -706,6 +749,7 @@ class _TwoTowerEngine(_FlatEngine):
         self.dpool_a, self.dpool_b, self.dpool_fus = f(B, D), f(B, D), f(B, D)
         self.d_fused = f(B, self.Nf, D)
         self.dx0_a, self.dx0_b = f(B * self.Na, D), f(B * self.Nb, D)
+        self._build_fusion()
         self.preds = torch.zeros(self._preds_shape(), dtype=torch.int32, device=dev)
         # M2M_EARLY_FUSION_WGRAD=1 (wide towers, small batch): the fusion tower's weight gradients on a side stream beside the
         # two modality towers' backward launches instead of inside the merged launch at the end.  Measured on MM-IMDb at its
@@ -766,6 +810,69 @@ class _TwoTowerEngine(_FlatEngine):
                             and self.t_a.wgrad_form(B) == 0 and self.t_fus.wgrad_form(B) == 0)
         self._pending_bump = False
 
+    def _build_fusion(self):
+        """Buffers of a fusion other than ConcatFusion: the towers' own outputs (B, N, D) and their input gradients; the gate's
+        descriptor (weights from the fp32 masters, gradients into the flat buffer), saved activations and partial sums."""
+        B, D, dev = self.B, self.D, self.device
+        self.out_a = self.out_b = self.d_out_a = self.d_out_b = None
+        self.gate = None
+        if self.concat:
+            return
+        f = lambda *s: torch.zeros(*s, device=dev)
+        self.out_a, self.out_b = f(B, self.Na, D), f(B, self.Nb, D)
+        if self.fusion_name == "SumFusion":
+            self.d_out_a = self.d_out_b = self.d_fused          # d(a + b) / da = d(a + b) / db = 1: both towers read d_fused
+        else:
+            self.d_out_a, self.d_out_b = f(B, self.Na, D), f(B, self.Nb, D)
+        if self.fusion_name != "BiModalGatedUnit":
+            return
+        rows = B * self.Nf
+        self._gate_bufs = dict(t1=f(rows, D), t2=f(rows, D), z=f(rows, D), dh=f(rows, 3 * D),
+                               part=f(int(L.lib().m2m_gate_part_floats(rows, D))))
+        g = L.Gate()
+        g.D = D
+        P, G = self.params, self.grads
+        for fld, key in (("w1", "mod1_hidden.weight"), ("b1", "mod1_hidden.bias"), ("w2", "mod2_hidden.weight"),
+                         ("b2", "mod2_hidden.bias"), ("wz", "z_hidden.weight"), ("bz", "z_hidden.bias")):
+            setattr(g, fld, P["fusion_function." + key].data_ptr())
+            setattr(g, "g_" + fld, G["fusion_function." + key].data_ptr())
+        for fld, t in self._gate_bufs.items():
+            setattr(g, fld, t.data_ptr())
+        self.gate = g
+
+    def _tower_outputs(self):
+        """(out_a, out_b, sample stride): where the two towers write their tokens."""
+        D = self.D
+        if self.concat:
+            return self.fused, self.fused.view(-1)[self.Na * D:], self.Nf * D
+        return self.out_a, self.out_b, None
+
+    def _fusion_forward(self, training: bool):
+        rows = self.B * self.Nf
+        if self.concat:
+            return
+        if self.gate is not None:
+            L.check(L.lib().m2m_gate_forward(C.byref(self.gate), self.out_a.data_ptr(), self.out_b.data_ptr(), self.fused.data_ptr(),
+                                             rows, int(training), L.stream_ptr()), "gate_forward")
+        else:
+            L.check(L.lib().m2m_fusion_forward(_ELEM_FUSION_MODE[self.fusion_name], self.out_a.data_ptr(), self.out_b.data_ptr(),
+                                               self.fused.data_ptr(), rows * self.D, L.stream_ptr()), "fusion_forward")
+
+    def _fusion_backward(self):
+        """d_fused -> the towers' output gradients (and the gate's weight gradients, added into flat_g: Adam clears them)."""
+        rows = self.B * self.Nf
+        if self.concat or self.fusion_name == "SumFusion":
+            return
+        if self.gate is not None:
+            L.check(L.lib().m2m_gate_backward(C.byref(self.gate), self.d_fused.data_ptr(), self.d_out_a.data_ptr(),
+                                              self.d_out_b.data_ptr(), rows, L.stream_ptr()), "gate_backward")
+            L.check(L.lib().m2m_gate_wgrad(C.byref(self.gate), self.out_a.data_ptr(), self.out_b.data_ptr(), rows, L.stream_ptr()),
+                    "gate_wgrad")
+        else:
+            L.check(L.lib().m2m_fusion_backward(_ELEM_FUSION_MODE[self.fusion_name], self.out_a.data_ptr(), self.out_b.data_ptr(),
+                                                self.d_fused.data_ptr(), self.d_out_a.data_ptr(), self.d_out_b.data_ptr(),
+                                                rows * self.D, L.stream_ptr()), "fusion_backward")
+
     def _preds_shape(self):
         return (3, self.B)
 
@@ -792,7 +899,8 @@ class _TwoTowerEngine(_FlatEngine):
         B, D = self.B, self.D
         sd = self.drop_step if training else None
         fs = self.Nf * D
-        b_part = self.fused.view(-1)[self.Na * D:]
+        out_a, b_part, ts = self._tower_outputs()
+        sa_, sb_ = (ts, ts) if self.concat else (self.Na * D, self.Nb * D)      # sample strides of the two towers' outputs
         main, side, _ = self._streams()
         so = 0                                               # host step offset of this pass's launches (see _embed_fold)
         pa, pb, pf = (None, None, None) if self._heads_pool else (self.pool_a, self.pool_b, self.pool_fus)
@@ -802,7 +910,7 @@ class _TwoTowerEngine(_FlatEngine):
             # the dropout counter advances in the weight-gradient launch of _backward (every launch in between gets step = 1)
             so, self._pending_bump = 1, True
             towers_forward([self.t_a, self.t_b],
-                           [(self.x0_a, self.Na * D, self.fused, fs, pa), (self.x0_b, self.Nb * D, b_part, fs, pb)],
+                           [(self.x0_a, self.Na * D, out_a, sa_, pa), (self.x0_b, self.Nb * D, b_part, sb_, pb)],
                            B, training, self.seed, so, sd, embeds=[self.e_a, self.e_b], inputs=[xa, xb],
                            head=(self.adam_state, self.losses))
         elif self.concurrent and can_group(self.t_a, self.t_b, self.B):
@@ -820,8 +928,8 @@ class _TwoTowerEngine(_FlatEngine):
                 self.e_a.forward(xa, B, self.x0_a)
                 self.e_b.forward(xb, B, self.x0_b)
             towers_forward([self.t_a, self.t_b],
-                           [(self.x0_a, self.Na * D, self.fused, fs, pa, sa, B * self.Na * D),
-                            (self.x0_b, self.Nb * D, b_part, fs, pb, sb, B * self.Nb * D)],
+                           [(self.x0_a, self.Na * D, out_a, sa_, pa, sa, B * self.Na * D),
+                            (self.x0_b, self.Nb * D, b_part, sb_, pb, sb, B * self.Nb * D)],
                            B, training, self.seed, 0, sd)
         else:
             if prologue:
@@ -829,10 +937,11 @@ class _TwoTowerEngine(_FlatEngine):
             side.wait_stream(main)
             with torch.cuda.stream(side):                   # second tower beside the first
                 self.e_b.forward(xb, B, self.x0_b)
-                self.t_b.forward(self.x0_b, self.Nb * D, B, b_part, fs, pb, training, self.seed, 0, sd)
+                self.t_b.forward(self.x0_b, self.Nb * D, B, b_part, sb_, pb, training, self.seed, 0, sd)
             self.e_a.forward(xa, B, self.x0_a)
-            self.t_a.forward(self.x0_a, self.Na * D, B, self.fused, fs, pa, training, self.seed, 0, sd)
+            self.t_a.forward(self.x0_a, self.Na * D, B, out_a, sa_, pa, training, self.seed, 0, sd)
             main.wait_stream(side)
+        self._fusion_forward(training and with_grad)
         self.t_fus.forward(self.fused, fs, B, self.fus_out, fs, pf, training, self.seed, so, sd)
         a, b = self.MODS
         hw = self.head_weights
@@ -840,8 +949,8 @@ class _TwoTowerEngine(_FlatEngine):
                  self._head(b, self.pool_b, self.dpool_b, hw[b], with_grad),
                  self._head("fusion", self.pool_fus, self.dpool_fus, hw["fusion"], with_grad)]
         if self._heads_pool:
-            heads[0]["tokens"] = (self.fused, self.Na, fs)
-            heads[1]["tokens"] = (b_part.data_ptr(), self.Nb, fs)
+            heads[0]["tokens"] = (out_a, self.Na, sa_)
+            heads[1]["tokens"] = (b_part.data_ptr(), self.Nb, sb_)
             heads[2]["tokens"] = (self.fus_out, self.Nf, fs)
         self._wgrad_heads = None
         if training and with_grad and self._head_part is not None:
@@ -868,7 +977,11 @@ class _TwoTowerEngine(_FlatEngine):
                                       self.d_fused, fs, self.seed, so, sd)
         else:
             self.t_fus.backward(B, None, 0, self.dpool_fus, self.d_fused, fs, self.seed, so, sd)
-        d_b_part = self.d_fused.view(-1)[self.Na * D:]
+        if self.concat:
+            d_a_part, d_b_part, sa_, sb_ = self.d_fused, self.d_fused.view(-1)[self.Na * D:], fs, fs
+        else:
+            self._fusion_backward()
+            d_a_part, d_b_part, sa_, sb_ = self.d_out_a, self.d_out_b, self.Na * D, self.Nb * D
         main, s_a, s_f = self._streams()
         wg_towers = [self.t_fus, self.t_a, self.t_b]
         if self._early_fus_wgrad:
@@ -885,13 +998,13 @@ class _TwoTowerEngine(_FlatEngine):
         # capture on ROCm 7.2.)
         if self.concurrent and can_group(self.t_a, self.t_b, self.B):
             towers_backward([self.t_a, self.t_b],
-                            [(self.d_fused, fs, self.dpool_a, self.dx0_a, self.Na * D), (d_b_part, fs, self.dpool_b, self.dx0_b, self.Nb * D)],
+                            [(d_a_part, sa_, self.dpool_a, self.dx0_a, self.Na * D), (d_b_part, sb_, self.dpool_b, self.dx0_b, self.Nb * D)],
                             B, self.seed, so, sd)
         else:
             s_a.wait_stream(main)
             with torch.cuda.stream(s_a):
-                self.t_a.backward(B, self.d_fused, fs, self.dpool_a, self.dx0_a, self.Na * D, self.seed, so, sd)
-            self.t_b.backward(B, d_b_part, fs, self.dpool_b, self.dx0_b, self.Nb * D, self.seed, so, sd)
+                self.t_a.backward(B, d_a_part, sa_, self.dpool_a, self.dx0_a, self.Na * D, self.seed, so, sd)
+            self.t_b.backward(B, d_b_part, sb_, self.dpool_b, self.dx0_b, self.Nb * D, self.seed, so, sd)
             main.wait_stream(s_a)
         bump = self.drop_step if self._pending_bump else None
         if can_group_embeds(self.e_a, self.e_b) and self.e_a.prec == self.t_a.prec and self.e_a.D == self.t_a.D:
