@@ -494,6 +494,27 @@ int m2m_gate_forward(const m2m_gate* g, const float* a, const float* b, float* y
 int m2m_gate_backward(const m2m_gate* g, const float* dy, float* da, float* db, int64_t rows, void* stream);
 int m2m_gate_wgrad(const m2m_gate* g, const float* a, const float* b, int64_t rows, void* stream);
 
+/* ---- accuracy / precision / recall / F1 count tables (additive within ABI 18; csrc/scores.hip) ---------------------------
+ * The reference keeps three dictionaries of torchmetrics objects per task module (setup_scores: models/avmnist.py:366-380,
+ * models/mimic.py:162-180, models/mmimdb.py:184-190) and calls metric(preds, labels) in every training / validation / test step
+ * (modules/train_test_module.py:72-84, :94-104, :132-142), compute() at the epoch ends (:86-92, :106-111, :144-151).  All of those
+ * scores are functions of small integer count tables.  These two calls ADD one batch's counts into a 64-bit device table (never
+ * overwrite: the caller clears it, e.g. hipMemsetAsync, at an epoch start); the derived numbers are host arithmetic on the
+ * table.  Integer atomics only: the result is exact and independent of the order of execution.
+ *
+ *   m2m_scores_multiclass  preds (nheads, B) int32 and labels (B) int64, as m2m_heads_ce holds them.  table: per head K * K + 1
+ *                          uint64, i.e. (nheads, K * K + 1): cell [head][label * K + pred] is the confusion matrix, the last
+ *                          cell of a head counts the rows whose label or prediction is outside [0, K) (they touch no other cell).
+ *                          K <= M2M_SCORES_MAX_CLASSES.
+ *   m2m_scores_multilabel  preds (nheads, B, K) int32 (non-zero: predicted) as m2m_heads_bce holds them, targets (B, K) float
+ *                          (positive when >= 0.5).  table (nheads, K, 4) uint64: tp, fp, fn, tn per label.
+ *                          K <= M2M_SCORES_MAX_LABELS.
+ * B >= 1 (any size); the table 8-byte aligned. */
+#define M2M_SCORES_MAX_CLASSES 64
+#define M2M_SCORES_MAX_LABELS 128
+int m2m_scores_multiclass(const int32_t* preds, const int64_t* labels, int nheads, int B, int K, uint64_t* table, void* stream);
+int m2m_scores_multilabel(const int32_t* preds, const float* targets, int nheads, int B, int K, uint64_t* table, void* stream);
+
 /* ---- test hooks ----------------------------------------------------------------------------------- */
 /* keep-mask (uint8, 1 keep) the kernels use for dropout site `site` (0 tok hidden, 1 tok out,
  * 2 channel hidden, 3 channel out) of block `blk` of tower t at (seed, step): rows x cols elements with

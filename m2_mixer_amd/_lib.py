@@ -96,6 +96,7 @@ class Head(C.Structure):
                 ("weight", C.c_float), ("g_part", _fp), ("tokens", _fp), ("tok_sample_stride", C.c_int64), ("ntok", C.c_int32)]
 
 
+SCORES_MAX_CLASSES, SCORES_MAX_LABELS = 64, 128    # m2m_scores_multiclass / _multilabel limits (M2M_SCORES_MAX_*)
 FUSION_SUM, FUSION_MEAN, FUSION_MAX = 1, 2, 3      # m2m_fusion_forward / _backward modes (M2M_FUSION_*)
 
 
@@ -179,6 +180,9 @@ SIGNATURES = {
     "m2m_gate_forward": (C.c_int, [C.POINTER(Gate), _fp, _fp, _fp, C.c_int64, C.c_int, _fp]),
     "m2m_gate_backward": (C.c_int, [C.POINTER(Gate), _fp, _fp, _fp, C.c_int64, _fp]),
     "m2m_gate_wgrad": (C.c_int, [C.POINTER(Gate), _fp, _fp, C.c_int64, _fp]),
+    # count tables of the scores (csrc/scores.hip): added into a uint64 device table
+    "m2m_scores_multiclass": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    "m2m_scores_multilabel": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "m2m_mlp_forward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, C.c_int, C.c_uint32, C.c_uint32,
                                   _fp, _fp]),
     "m2m_mlp_backward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, _fp]),

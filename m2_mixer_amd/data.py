@@ -144,8 +144,18 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
                         the quantity ReduceLROnPlateau / EarlyStopping monitor (run.py:61-67, models/avmnist.py:416-422)
       loss_step_mean    plain mean over steps = the wandb `val_loss` / `train_loss` number (train_test_module.py:92, :113)
       loss_image / loss_audio / loss_fusion   step means (models/avmnist.py:326-337)
-      acc, acc_image, acc_audio, hits*, steps, samples"""
+      acc, acc_image, acc_audio, hits*, steps, samples
+    An engine built with scores=True also counts the pass into its table of `split` (engine.score_table: cleared here at the
+    start, read once at the end -- it stays readable until the next pass over the split) and the reference's scores derived
+    from it are added under their own names (`f1m`, `prec_m`, `rec_m`, ..., `f1m_image`, ...: scores.TASK_SCORES); the keys
+    above keep their values -- the table's `acc` is the same quotient as the hit count's."""
     dev = engine.device
+    table = None
+    if getattr(engine, "scores", None) is not None:
+        # a training pass counts into the training table (the captured step adds there); an evaluating pass into `split`'s own
+        table = engine.score_table("train" if train else (split if split != "train" else "train_eval"))
+    if table is not None:
+        table.reset()
     # [loss_a, loss_b, loss_fusion, loss] step sums | the same weighted by the step's batch size | hits a, b, fusion
     acc = torch.zeros(11, device=dev, dtype=torch.float64)
     seen, host = 0, np.zeros(11)
@@ -175,7 +185,7 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
             else:
                 eng.train_step(image, audio, labels, grad_sync=grad_sync)
         else:
-            eng.evaluate(image, audio, labels)
+            eng.evaluate(image, audio, labels, **({} if table is None else {"scores": table}))
         if eng is not engine and train:
             engine.pack()                                          # the tail step changed the weights
         acc[:4] += eng.losses                                      # device-side: no host round trip
@@ -188,8 +198,10 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
                 log({"split": split, "step": i + 1, "loss": host[3] / (i + 1), "acc": host[10] / seen})
     steps, n = max(nb, 1), max(seen, 1)
     a, b = getattr(engine, "MODS", ("image", "audio"))
-    return {"loss": float(host[7]) / n, "loss_step_mean": float(host[3]) / steps,
+    out = {} if table is None else table.compute()
+    out.update({"loss": float(host[7]) / n, "loss_step_mean": float(host[3]) / steps,
             f"loss_{a}": float(host[0]) / steps, f"loss_{b}": float(host[1]) / steps, "loss_fusion": float(host[2]) / steps,
             "acc": float(host[10]) / n, f"acc_{a}": float(host[8]) / n, f"acc_{b}": float(host[9]) / n,
             "hits": int(round(host[10])), f"hits_{a}": int(round(host[8])), f"hits_{b}": int(round(host[9])),
-            "steps": nb, "samples": seen}
+            "steps": nb, "samples": seen})
+    return out

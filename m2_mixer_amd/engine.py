@@ -13,7 +13,9 @@ What changes relative to the module path (modules/mixer.py + torch autograd):
   * the three heads, their losses and gradients are one launch;
   * each tower's Adam update + operand re-pack follows its own weight gradients on its own HIP stream;
   * the step can be captured into a hipGraph (torch.cuda.CUDAGraph); the dropout step counter, the Adam
-    step counter and the learning rate live in device memory so replays stay correct.
+    step counter and the learning rate live in device memory so replays stay correct;
+  * scores=True: the step also adds its batch's counts into an integer table on the device (ScoreTable, csrc/scores.hip), from
+    which accuracy / precision / recall / F1 under the reference's names are derived once per epoch (scores.py).
 """
 from __future__ import annotations
 
@@ -145,13 +147,65 @@ def _is_layer_norm(k: str) -> bool:
         or k.endswith("channel_mix.0.weight") or k.endswith("channel_mix.0.bias")
 
 
+class ScoreTable:
+    """The count table of one split (train / val / test) in device memory: every step ADDS its batch's counts (csrc/scores.hip,
+    one launch, capturable), the host reads it once per epoch and derives the reference's scores in float64 (scores.py).
+    kind "multiclass": per head a (K, K) confusion matrix [label][pred] + one cell of skipped rows (label or prediction outside
+    [0, K)); "multilabel": per head (K, 4) = tp, fp, fn, tn per label."""
+
+    def __init__(self, task: str, head_names: Sequence[str], K: int, device):
+        from . import scores as S
+        self.task, self.kind, self.head_names, self.K = task, S.TASK_KIND[task], tuple(head_names), int(K)
+        lim = L.SCORES_MAX_LABELS if self.kind == "multilabel" else L.SCORES_MAX_CLASSES
+        if not 1 <= self.K <= lim:
+            raise RuntimeError(f"ScoreTable: {self.kind} K = {K}: the scores kernel takes 1..{lim}")
+        self.cells = self.K * 4 if self.kind == "multilabel" else self.K * self.K + 1
+        self.table = torch.zeros(len(self.head_names), self.cells, dtype=torch.int64, device=device)
+        self.skipped = None                          # multiclass: per-head skipped rows as of the last counts()
+
+    def add(self, preds: torch.Tensor, truth: torch.Tensor):
+        """Enqueue the launch that adds one batch: preds int32 (nheads, B) / (nheads, B, K), truth int64 labels (B) / float
+        targets (B, K).  Nothing synchronises."""
+        nh, B = len(self.head_names), int(preds.shape[1])
+        ml = self.kind == "multilabel"
+        want_p, want_t = ((nh, B, self.K), (B, self.K)) if ml else ((nh, B), (B,))
+        if (tuple(preds.shape) != want_p or tuple(truth.shape) != want_t or preds.dtype != torch.int32
+                or truth.dtype != (torch.float32 if ml else torch.int64) or not preds.is_contiguous() or not truth.is_contiguous()
+                or preds.device != self.table.device or truth.device != self.table.device):
+            raise RuntimeError(f"ScoreTable.add: {self.kind} needs contiguous device tensors preds int32 {want_p} and "
+                               f"{'targets float32' if ml else 'labels int64'} {want_t}")
+        fn = L.lib().m2m_scores_multilabel if ml else L.lib().m2m_scores_multiclass
+        L.check(fn(preds.data_ptr(), truth.data_ptr(), nh, B, self.K, self.table.data_ptr(), L.stream_ptr()), "scores_" + self.kind)
+
+    def reset(self):
+        """Clear the table: an asynchronous fill on the current stream, in place -- captured graphs keep adding into it."""
+        self.table.zero_()
+
+    def counts(self) -> torch.Tensor:
+        """The table on the host, int64: (nheads, K, K) or (nheads, K, 4).  One device-to-host copy: the only synchronisation."""
+        host = self.table.cpu()
+        if self.kind == "multilabel":
+            return host.view(-1, self.K, 4)
+        self.skipped = host[:, -1].clone()
+        return host[:, :-1].reshape(-1, self.K, self.K)
+
+    def compute(self) -> Dict[str, float]:
+        """The reference's score names of this task -> float (fusion head: plain names; other heads: `_<modality>` appended)."""
+        from . import scores as S
+        return S.task_scores(self.task, self.counts().numpy(), self.head_names)
+
+
 class _FlatEngine:
     """Flat parameter / gradient / Adam buffers, the optimizer, data-parallel hooks and hipGraph capture.
     Subclasses supply `shapes`, `_segment_of(key)`, `_build()`, `_forward(...)`, `_backward(...)`, `pack()`."""
 
     SEGMENTS: Tuple[str, ...] = ()
 
-    def __init__(self, cfg: dict, batch_size: int, device, precision, lr, betas, eps, weight_decay, seed, init, share=None):
+    #: the task whose score names a ScoreTable of this engine reports (scores.TASK_SCORES)
+    SCORES_TASK: str = ""
+
+    def __init__(self, cfg: dict, batch_size: int, device, precision, lr, betas, eps, weight_decay, seed, init, share=None,
+                 scores: bool = False):
         """share: another engine of the same model; this one then works on ITS parameters, gradients, Adam state and
         step counters (its own activation buffers and packed operand copies, for another batch size) -- the second,
         smaller step that takes the ragged last batch of an epoch (data.run_epoch).  After a step on one of the two
@@ -210,6 +264,13 @@ class _FlatEngine:
             self.loss_weights = torch.tensor(self._head_weight_list(), dtype=torch.float32, device=dev)
             self._loss_weight_group = {"fused_heads": False}      # (shared by the siblings, like the table itself)
         self.seed = (share.seed if share is not None else seed) & 0xFFFFFFFF
+        # scores=True: every training step ends its forward with one launch that adds the batch's counts into `self.scores`
+        # (a sibling adds into its parent's table); off: no table, no launch -- the step is exactly the one without the feature
+        self.scores: Optional[ScoreTable] = None
+        if share is not None:
+            self.scores = share.scores
+        elif scores:
+            self.scores = self.new_score_table()
         if init and share is None:
             self.reset_parameters(seed)
         self.logits = torch.zeros(3, self.B, self.K, device=dev)
@@ -475,7 +536,9 @@ class _FlatEngine:
         self._check_trains()
         self._slots_folded = False
         self._forward(*batch, training=True, with_grad=True, prologue=True)
+        self._score_forward(batch[-1])
         self._backward(*batch[:-1])
+        self._score_backward(batch[-1])
         for t in self._slot_towers:
             t.wgrad_fold()
         self._slots_folded = True                       # (consumed by the optimizer_step that follows; fused_step resets it)
@@ -487,8 +550,39 @@ class _FlatEngine:
         # Adam skip the slot of the two-group tower: the slot is folded by forward_backward only)
         self._slots_folded = False
         self._forward(*batch, training=True, with_grad=True, prologue=True)
+        self._score_forward(batch[-1])
         self._backward(*batch[:-1], fused_update=True)
+        self._score_backward(batch[-1])
         return self.losses
+
+    # ---- scores ----------------------------------------------------------------------------------------------
+    def new_score_table(self) -> ScoreTable:
+        """An empty count table for this model's heads (one per split: evaluate(..., scores=table) adds into the one given)."""
+        return ScoreTable(self.SCORES_TASK, self.HEAD_NAMES, self.K, self.device)
+
+    def score_table(self, split: str) -> ScoreTable:
+        """The table of `split`, kept on the engine: "train" is the training table (`self.scores`, which needs scores=True),
+        any other name gets a table of its own on first use."""
+        if split == "train":
+            if self.scores is None:
+                raise RuntimeError("score_table('train'): this engine was built with scores=False")
+            return self.scores
+        tables = self.__dict__.setdefault("_split_scores", {})
+        if split not in tables:
+            tables[split] = self.new_score_table()
+        return tables[split]
+
+    def _preds_in_forward(self) -> bool:
+        """Whether a training forward leaves `preds` written (False: the heads ride in the fusion tower's backward launch)."""
+        return not getattr(self, "_fused_heads", False)
+
+    def _score_forward(self, truth):
+        if self.scores is not None and self._preds_in_forward():
+            self.scores.add(self.preds, truth)
+
+    def _score_backward(self, truth):
+        if self.scores is not None and not self._preds_in_forward():
+            self.scores.add(self.preds, truth)
 
     def _check_trains(self):
         if getattr(self, "_eval_only", False):
@@ -608,7 +702,10 @@ class _FlatEngine:
         st = slots[0]
         # The warm-up below runs REAL training steps (lazy initialisation of the launches must happen outside the capture).
         # Everything they change is put back afterwards, so capture() leaves the model exactly as it found it.
-        snap = [t.clone() for t in (self.flat_p, self.flat_m, self.flat_v, self.flat_g, self.adam_state, self.drop_step)]
+        state = [self.flat_p, self.flat_m, self.flat_v, self.flat_g, self.adam_state, self.drop_step]
+        if self.scores is not None:
+            state.append(self.scores.table)          # (the warm-up steps count their batch too)
+        snap = [t.clone() for t in state]
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
@@ -626,7 +723,7 @@ class _FlatEngine:
                     self.optimizer_step(scale, getattr(grad_sync, "reduced_bf16", None))
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        for dst, src in zip((self.flat_p, self.flat_m, self.flat_v, self.flat_g, self.adam_state, self.drop_step), snap):
+        for dst, src in zip(state, snap):
             dst.copy_(src)
         self.pack()
         torch.cuda.synchronize()
@@ -1039,9 +1136,12 @@ class _TwoTowerEngine(_FlatEngine):
         return [(lo, hi, mods[name]) for name, (lo, hi) in segs]
 
     @torch.no_grad()
-    def evaluate(self, xa, xb, labels):
-        """validation/test step: dropout off (the reference's shared_step under model.eval())."""
+    def evaluate(self, xa, xb, labels, scores: Optional[ScoreTable] = None):
+        """validation/test step: dropout off (the reference's shared_step under model.eval()).  scores: a table
+        (new_score_table / score_table(split)) this batch's counts are added into."""
         self._forward(xa, xb, labels, False, False)
+        if scores is not None:
+            scores.add(self.preds, labels)
         a, b = self.MODS
         return {"logits": self.logits[2], f"{a}_logits": self.logits[0], f"{b}_logits": self.logits[1],
                 f"loss_{a}": self.losses[0], f"loss_{b}": self.losses[1], "loss_fusion": self.losses[2],
@@ -1056,15 +1156,16 @@ class AVMnistEngine(_TwoTowerEngine):
 
     def __init__(self, cfg: dict, batch_size: int, device="cuda:0", precision: Optional[str] = None,
                  lr: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 fusion_loss_weight: float = 1.0 / 3, seed: int = 42, init: bool = True, share=None):
+                 fusion_loss_weight: float = 1.0 / 3, seed: int = 42, init: bool = True, share=None, scores: bool = False):
         w = fusion_loss_weight
         ow = (1 - w) / 2
         # loss = (w Lf + ow Li + ow La) * 3      (models/avmnist.py:289-290)
         self.head_weights = {"image": 3 * ow, "audio": 3 * ow, "fusion": 3 * w}
         self.fusion_loss_weight = w
-        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share)
+        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share, scores)
 
     HEAD_NAMES = ("image", "audio", "fusion")
+    SCORES_TASK = "avmnist"
 
     def set_fusion_loss_weight(self, w: float):
         ow = (1 - w) / 2
@@ -1095,14 +1196,15 @@ class MMIMDBEngine(_TwoTowerEngine):
 
     MODS = ("image", "text")
     HEAD_NAMES = ("image", "text", "fusion")
+    SCORES_TASK = "mmimdb"
     #: buffers of the three BCEWithLogitsLoss modules in the reference's state_dict (models/mmimdb.py:47-50)
     EXTRA_STATE_KEYS = ("image_criterion.pos_weight", "text_criterion.pos_weight", "fusion_criterion.pos_weight")
 
     def __init__(self, cfg: dict, batch_size: int, device="cuda:0", precision: Optional[str] = None,
                  lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 seed: int = 42, init: bool = True, share=None):
+                 seed: int = 42, init: bool = True, share=None, scores: bool = False):
         self.head_weights = {"image": 1.0, "text": 1.0, "fusion": 1.0}
-        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share)
+        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share, scores)
         self.pos_weight = torch.tensor(cfg["pos_weight"], dtype=torch.float32, device=self.device)
         if self.pos_weight.numel() != self.K:
             raise RuntimeError("pos_weight needs one entry per class")
@@ -1134,14 +1236,15 @@ class MimicEngine(_FlatEngine):
 
     def __init__(self, cfg: dict, batch_size: int, device="cuda:0", precision: Optional[str] = None,
                  lr: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 fusion_loss_weight: float = 1.0 / 3, seed: int = 42, init: bool = True, share=None):
+                 fusion_loss_weight: float = 1.0 / 3, seed: int = 42, init: bool = True, share=None, scores: bool = False):
         w = fusion_loss_weight
         ow = (1 - w) / 2
         self.head_weights = {"static": ow, "time": ow, "fusion": w}
         self.fusion_loss_weight = w
-        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share)
+        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share, scores)
 
     HEAD_NAMES = ("static", "time", "fusion")
+    SCORES_TASK = "mimic"
 
     def set_fusion_loss_weight(self, w: float):
         ow = (1 - w) / 2
@@ -1287,8 +1390,10 @@ class MimicEngine(_FlatEngine):
         main.wait_stream(s_f)
 
     @torch.no_grad()
-    def evaluate(self, static, time, labels):
+    def evaluate(self, static, time, labels, scores: Optional[ScoreTable] = None):
         self._forward(static, time, labels, False, False)
+        if scores is not None:
+            scores.add(self.preds, labels)
         return {"logits": self.logits[2], "logits_static": self.logits[0], "logits_time": self.logits[1],
                 "loss_static": self.losses[0], "loss_time": self.losses[1], "loss_fusion": self.losses[2],
                 "loss": self.losses[3], "preds": self.preds[2]}

@@ -275,9 +275,9 @@ class _MultiLossModule(nn.Module):
         return dict(lr=oc.get("lr", oc.get("learning_rate", 1e-3)), betas=tuple(oc.get("betas", (0.9, 0.999))),
                     eps=oc.get("eps", 1e-8), weight_decay=oc.get("weight_decay", 0.0))
 
-    def to_engine(self, batch_size: int, precision: Optional[str] = None):
-        """The fused training engine (engine.py) over a copy of this module's weights."""
-        eng = self._make_engine(self._engine_cfg(), batch_size, next(self.parameters()).device, precision)
+    def to_engine(self, batch_size: int, precision: Optional[str] = None, scores: bool = False):
+        """The fused training engine (engine.py) over a copy of this module's weights.  scores: see bind_engine."""
+        eng = self._make_engine(self._engine_cfg(), batch_size, next(self.parameters()).device, precision, scores=scores)
         eng.load_state_dict(self.state_dict())
         return eng
 
@@ -287,7 +287,7 @@ class _MultiLossModule(nn.Module):
         """The fused engine this module is bound to (bind_engine), or None."""
         return self._engine
 
-    def bind_engine(self, batch_size: int, precision: Optional[str] = None):
+    def bind_engine(self, batch_size: int, precision: Optional[str] = None, scores: bool = False):
         """Engine-backed mode: build the fused engine (engine.py) for `batch_size`, copy this module's weights into it, then
         point every parameter's `.data` at the engine's buffer (`engine.params[key]`): the Parameter objects stay the same,
         `parameters()`, `state_dict()`, `save_checkpoint()` read the live weights, and no copy is taken again.  From then on
@@ -295,7 +295,11 @@ class _MultiLossModule(nn.Module):
         returns an EngineOptimizer and validation_epoch_end forwards the loss-weight schedule to the engine.
         A LightningModule subclass sets `automatic_optimization = False` when bound: the replayed step already updated the
         weights (EngineOptimizer.step is a no-op).  Refused: epoch-triggered freezing and random muting (the engine trains every
-        parameter and has no muting); a fixed `mute` is supported."""
+        parameter and has no muting); a fixed `mute` is supported.
+        scores=True: training_step / validation_step / test_step also add their batch's counts into the train / val / test count
+        tables on the device (the reference's three setup_scores dictionaries; one small launch per step, inside the captured
+        graph for training), and training_epoch_end / validation_epoch_end / test_epoch_end return the reference's scores.
+        Off (the default): no table, no launch."""
         if self._engine is not None:
             raise RuntimeError("bind_engine: this module is already bound to an engine")
         if self.freeze_modalities_on_epoch is not None or self.modalities_freezed:
@@ -305,7 +309,7 @@ class _MultiLossModule(nn.Module):
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("bind_engine: the module must be on the GPU (.to('cuda')) first; the engine has no CPU path")
-        eng = self._make_engine(self._engine_cfg(), batch_size, dev, precision)
+        eng = self._make_engine(self._engine_cfg(), batch_size, dev, precision, scores=scores)
         eng.load_state_dict(self.state_dict())
         with torch.no_grad():
             for k, p in self.named_parameters():
@@ -433,8 +437,39 @@ class _MultiLossModule(nn.Module):
             return self.shared_step(batch, mode=mode)
         xa, xb, labels = self._engine_batch(batch, train=False)
         sib = self._eval_sibling(labels.shape[0])
-        sib.evaluate(xa.contiguous(), xb.contiguous(), labels.contiguous())
+        table = self._score_table(mode)
+        if table is None:
+            sib.evaluate(xa.contiguous(), xb.contiguous(), labels.contiguous())
+        else:
+            sib.evaluate(xa.contiguous(), xb.contiguous(), labels.contiguous(), scores=table)
         return self._engine_eval_outputs(sib, batch, labels)
+
+    def _score_table(self, split: str):
+        """The bound engine's count table of `split` ("train", "val", "test"); None when unbound, bound without scores, or bound
+        to an engine that has none."""
+        eng = self._engine
+        if eng is None or getattr(eng, "scores", None) is None:
+            return None
+        return eng.score_table(split)
+
+    def _epoch_scores(self, split: str) -> Optional[Dict[str, float]]:
+        """compute() of `split`'s table under the reference's logging names (`<split>_<metric>`), then reset it -- what the
+        torchmetrics objects do at an epoch end under Lightning.  One device-to-host copy."""
+        table = self._score_table(split)
+        if table is None:
+            return None
+        out = {f"{split}_{k}": v for k, v in table.compute().items()}
+        table.reset()
+        return out
+
+    def training_epoch_end(self, outputs=None) -> Optional[Dict[str, float]]:
+        """modules/train_test_module.py:86-92: {"train_<metric>": float} of the epoch's training steps (bound with scores=True;
+        else None); the training table starts the next epoch empty."""
+        return self._epoch_scores("train")
+
+    def test_epoch_end(self, outputs=None) -> Optional[Dict[str, float]]:
+        """modules/train_test_module.py:144-151: {"test_<metric>": float} (bound with scores=True; else None)."""
+        return self._epoch_scores("test")
 
     def validation_step(self, batch, batch_idx: int = 0) -> Dict[str, torch.Tensor]:
         """modules/train_test_module.py:94-104.  Bound: the engine's evaluation (dropout off) through an evaluating sibling per
@@ -448,18 +483,22 @@ class _MultiLossModule(nn.Module):
     #: whether validation_epoch_end applies the fusion-loss-weight schedule (the reference's AV-MNIST and MIMIC models do)
     LOSS_SCHEDULE = True
 
-    def validation_epoch_end(self, outputs=None) -> None:
+    def validation_epoch_end(self, outputs=None) -> Optional[Dict[str, float]]:
         """The loss-weight schedule of models/avmnist.py:338-339 / models/mimic.py:149-150: from epoch `loss_change_epoch` on,
         fusion_loss_weight grows by `fusion_loss_change` per validation epoch, up to 1.  Bound: forwarded to the engine, whose
-        captured step reads the new coefficients on its next replay.  (The reference's logging part is Lightning's.)"""
+        captured step reads the new coefficients on its next replay.  Bound with scores=True it also returns
+        {"val_<metric>": float} (modules/train_test_module.py:106-111) and resets the validation table; else None.
+        (The reference's logging part is Lightning's.)"""
+        scores = self._epoch_scores("val")
         if not self.LOSS_SCHEDULE or self.current_epoch < self.loss_change_epoch:
-            return
+            return scores
         new = min(1, self.fusion_loss_weight + self.fusion_loss_change)
         if new == self.fusion_loss_weight:
-            return
+            return scores
         if self._engine is not None:
             self._engine.set_fusion_loss_weight(float(new))
         self.fusion_loss_weight = new
+        return scores
 
 
 class AVMnistMixerMultiLoss(_MultiLossModule):
@@ -506,10 +545,10 @@ class AVMnistMixerMultiLoss(_MultiLossModule):
     def _engine_batch(self, batch, train):
         return self._two_tower_batch(batch, train, batch["label"].long())
 
-    def _make_engine(self, cfg, batch_size, device, precision):
+    def _make_engine(self, cfg, batch_size, device, precision, scores=False):
         from .engine import AVMnistEngine
         return AVMnistEngine(cfg, batch_size, device=device, precision=precision,
-                             fusion_loss_weight=self.fusion_loss_weight, init=False, **self._engine_kwargs())
+                             fusion_loss_weight=self.fusion_loss_weight, init=False, scores=scores, **self._engine_kwargs())
 
 
 class MMIMDBMixerMultiLoss(_MultiLossModule):
@@ -582,9 +621,9 @@ class MMIMDBMixerMultiLoss(_MultiLossModule):
         if any(not torch.equal(pw[0].cpu(), p.cpu()) for p in pw[1:]):
             raise RuntimeError("the bound engine takes one pos_weight for all three heads (models/mmimdb.py:47-50 builds them equal)")
 
-    def _make_engine(self, cfg, batch_size, device, precision):
+    def _make_engine(self, cfg, batch_size, device, precision, scores=False):
         from .engine import MMIMDBEngine
-        return MMIMDBEngine(cfg, batch_size, device=device, precision=precision, init=False, **self._engine_kwargs())
+        return MMIMDBEngine(cfg, batch_size, device=device, precision=precision, init=False, scores=scores, **self._engine_kwargs())
 
 
 class MimicMixerMultiLoss(_MultiLossModule):
@@ -632,7 +671,7 @@ class MimicMixerMultiLoss(_MultiLossModule):
                 "loss_fusion": l[2], "loss_static": l[0], "loss_time": l[1], "logits": lg[2], "logits_static": lg[0],
                 "logits_time": lg[1]}
 
-    def _make_engine(self, cfg, batch_size, device, precision):
+    def _make_engine(self, cfg, batch_size, device, precision, scores=False):
         from .engine import MimicEngine
         return MimicEngine(cfg, batch_size, device=device, precision=precision,
-                           fusion_loss_weight=self.fusion_loss_weight, init=False, **self._engine_kwargs())
+                           fusion_loss_weight=self.fusion_loss_weight, init=False, scores=scores, **self._engine_kwargs())
