@@ -414,6 +414,8 @@ int m2m_mlp_ride_flush(void* stream);
  * step count from it, so a captured graph can be replayed while the host edits lr.  With bump_step != 0
  * state[0] is incremented on the stream first; a step may be applied as several calls over disjoint
  * segments of the flat buffers (bump once, n == 0 allowed), e.g. per tower as its gradients complete. */
+/* 1 - beta is the float difference 1.0f - beta (0.00099998713 for 0.999f), not torch.optim.Adam's double difference rounded once
+ * (0.001f): exp_avg_sq sits 1.3e-5 relative below float32 torch at the default betas; tests/test_gpu_adam.py holds it to that. */
 int m2m_adam_step(float* param, float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
                   float* state, float beta1, float beta2, float eps, float weight_decay,
                   float grad_scale, int bump_step, void* stream);
@@ -523,9 +525,15 @@ int m2m_dropout_mask(const m2m_tower* t, int blk, int site, int B, uint32_t seed
                      uint8_t* mask, void* stream);
 /* y = gelu(x), dy = gelu'(x) elementwise with the device implementation (n floats). */
 int m2m_gelu_probe(const float* x, float* y, float* dy, int64_t n, void* stream);
+/* The same through the bf16 path's 512-cell piecewise-linear LDS tables (additive within ABI 18): ONE workgroup fills the table
+ * for dropout scale `scale` with the chain kernels' own fill function and evaluates y = gelu(x) * scale, dy = gelu'(x) * scale
+ * through the functions they call.  form 0: the fp32 table; 1: the forward-only table (dy is not written, may be NULL);
+ * 2: the fp16 table of the backward; 3: the fp16 table under a zero keep-mask (a dropped element: y = dy = 0 exactly);
+ * 4: no table, y = exp(-x^2 / 2) as the fp32 gelu' evaluates it (dy is not written, may be NULL; scale is ignored). */
+int m2m_gelu_table_probe(int form, const float* x, float* y, float* dy, int64_t n, float scale, void* stream);
 /* C (I x J, fp32) = A (I x K) * B(J x K)^T through pack + MFMA, mode_b 0: B packed NAT, plain product;
  * 1: chained: C = (A B^T) is fed as operand of a second product with Bc (J2 x J): C2 = C * Bc^T.
- * Exercises the fragment layouts end to end. */
+ * Exercises the fragment layouts end to end (tests/test_gpu_probes.py).  workspace: m2m_packed_bytes of A, Bm and Bc, back to back. */
 int m2m_gemm_probe(int prec, const float* A, const float* Bm, int I, int J, int K,
                    const float* Bc, int J2, float* C, float* C2, void* workspace, void* stream);
 

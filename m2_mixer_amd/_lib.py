@@ -202,6 +202,7 @@ SIGNATURES = {
     "m2m_adam_pack_all": (C.c_int, [C.POINTER(C.POINTER(Tower)), C.c_int, C.POINTER(C.POINTER(Embed)), C.c_int, _fp, _fp, _fp]),
     "m2m_dropout_mask": (C.c_int, [C.POINTER(Tower), C.c_int, C.c_int, C.c_int, C.c_uint32, C.c_uint32, _fp, _fp]),
     "m2m_gelu_probe": (C.c_int, [_fp, _fp, _fp, C.c_int64, _fp]),
+    "m2m_gelu_table_probe": (C.c_int, [C.c_int, _fp, _fp, _fp, C.c_int64, C.c_float, _fp]),
     "m2m_gemm_probe": (C.c_int, [C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, _fp, _fp, _fp]),
     "m2m_clock_probe": (C.c_int, [_fp, C.c_int, C.c_int, _fp]),
 }

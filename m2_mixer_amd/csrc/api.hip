@@ -476,15 +476,17 @@ static int adam_launch(float* param, float* grad, const void* grad_bf16, float* 
                        float beta1, float beta2, float eps, float weight_decay, float grad_scale, int bump_step,
                        const m2m_grad_range* ranges, int nranges, void* stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    // every refusal comes before the first launch (the step count's bump included): -1 means nothing ran
+    if (nranges < 0 || nranges > M2M_MAX_GRAD_RANGES || (nranges > 0 && !ranges)) { m2m_set_error("adam_step: bad ranges", __FILE__, __LINE__); return -1; }
+    for (int r = 0; r < nranges; ++r)
+        if (ranges[r].lo < 0 || ranges[r].n < 0 || ranges[r].lo + ranges[r].n > (n > 0 ? n : 0)) { m2m_set_error("adam_step_ranges: range outside the buffers", __FILE__, __LINE__); return -1; }
     if (bump_step) hipLaunchKernelGGL(adam_bump_kernel, dim3(1), dim3(1), 0, st, state);
     if (n <= 0) return 0;
-    if (nranges < 0 || nranges > M2M_MAX_GRAD_RANGES || (nranges > 0 && !ranges)) { m2m_set_error("adam_step: bad ranges", __FILE__, __LINE__); return -1; }
     const long head = 0;                                         // (4-byte accesses: no alignment requirement on the segment)
     AdamRanges rg;
     memset(&rg, 0, sizeof(rg));
     rg.n = nranges;
     for (int r = 0; r < nranges; ++r) {
-        if (ranges[r].lo < 0 || ranges[r].n < 0 || ranges[r].lo + ranges[r].n > n) { m2m_set_error("adam_step_ranges: range outside the buffers", __FILE__, __LINE__); return -1; }
         rg.lo[r] = (long)ranges[r].lo - head; rg.hi[r] = (long)(ranges[r].lo + ranges[r].n) - head;
         rg.add[r] = ranges[r].add; rg.keep[r] = ranges[r].keep;
     }
@@ -1164,6 +1166,41 @@ extern "C" int m2m_gelu_probe(const float* x, float* y, float* dy, int64_t n, vo
     return 0;
 }
 
+// gelu / gelu' through the bf16 path's LDS tables: one workgroup fills the table with the chain kernels' own fill function and
+// evaluates through the functions they call.  form 0: fp32 table {a, b, c, d}; 1: forward-only table {a, b} (dy not written);
+// 2: fp16 table; 3: fp16 table through gelu_grad_tabh_masked with mask 0 (a dropped element: exact zeros);
+// 4: y = the exp(-x^2 / 2) factor of gelu_grad_f as the device evaluates it (no table; dy not written).
+__global__ __launch_bounds__(256) void gelu_table_probe_kernel(int form, const float* __restrict__ x, float* __restrict__ y,
+                                                               float* __restrict__ dy, long n, float scale) {
+    __shared__ __attribute__((aligned(16))) char tabmem[GELU_TAB_N * sizeof(gtab_t)];
+    gtab_t* tab = reinterpret_cast<gtab_t*>(tabmem);
+    gtab2_t* tab2 = reinterpret_cast<gtab2_t*>(tabmem);
+    gtabh_t* tabh = reinterpret_cast<gtabh_t*>(tabmem);
+    const int tid = threadIdx.x;
+    if (form == 0) gelu_tab_fill(tab, scale, tid, 256);
+    else if (form == 1) gelu_tab2_fill(tab2, scale, tid, 256);
+    else if (form == 2 || form == 3) gelu_tabh_fill(tabh, scale, tid, 256);
+    __syncthreads();
+    for (long i = tid; i < n; i += 256) {
+        const float v = x[i];
+        float g = 0.f, dg = 0.f;
+        if (form == 0) Act<PREC_BF16>::gelu_grad_scaled(tab, v, scale, g, dg);
+        else if (form == 1) g = Act<PREC_BF16>::gelu_scaled(tab2, v, scale);
+        else if (form == 2) Act<PREC_BF16>::gelu_grad_scaled(tabh, v, scale, g, dg);
+        else if (form == 3) gelu_grad_tabh_masked(tabh, v, 0u, g, dg);
+        else g = gelu_exp_f(v);
+        y[i] = g;
+        if (form != 1 && form != 4) dy[i] = dg;
+    }
+}
+extern "C" int m2m_gelu_table_probe(int form, const float* x, float* y, float* dy, int64_t n, float scale, void* stream) {
+    if (form < 0 || form > 4 || !x || !y || n < 0 || (!dy && form != 1 && form != 4)) { m2m_set_error("gelu_table_probe: bad arguments", __FILE__, __LINE__); return -1; }
+    if (n == 0) return 0;
+    hipLaunchKernelGGL(gelu_table_probe_kernel, dim3(1), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), form, x, y, dy, (long)n, scale);
+    M2M_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 // Mirrors the kernels' mask functions.  mode 0: generic 16-bit draw per element index;
 // mode 1 (token sites at p == 0.5): one word per row (row = sample*D + channel), bit = column;
 // mode 2 (channel-hidden site): drop_keep_mc on (row, column).
@@ -1214,6 +1251,7 @@ __global__ void gemm_probe_kernel(const char* Ap /*NAT [i][k] k-minor*/, const c
     const int nKB = (K + Pr::KB - 1) / Pr::KB;
     const int nJT = (J + 15) / 16;
     const int nJ2T = (J2 + 15) / 16;
+    const int nKBc = (J + Pr::KB - 1) / Pr::KB;      // k-blocks of the packed Bc image (k = j)
     // swapped product: Ct[j][i] = B A^T so that the accumulator (rows j) chains into k = j
     for (int jp = 0; jp < (nJT + 1) / 2; ++jp) {
         f32x4_t acc[2];
@@ -1235,7 +1273,10 @@ __global__ void gemm_probe_kernel(const char* Ap /*NAT [i][k] k-minor*/, const c
         if (C2) {
             Frag hf[Chain<P>::NF];
             Chain<P>::make(acc[0], acc[1], hf);
-            for (int f = 0; f < Chain<P>::NF; ++f)
+            for (int f = 0; f < Chain<P>::NF; ++f) {
+                // fp32 chains one k-block per j tile: with an odd number of j tiles the pair's second fragment is empty and its
+                // k-block lies past the packed image (zero accumulator x unowned bytes: NaN bytes there would poison C2)
+                if (jp * Chain<P>::NF + f >= nKBc) continue;
                 for (int j2t = 0; j2t < nJ2T; ++j2t) {
                     const Frag w = ld_frag_global(Bcp, (long)(jp * Chain<P>::NF + f) * nJ2T + j2t, lane);
                     f32x4_t o = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -1245,6 +1286,7 @@ __global__ void gemm_probe_kernel(const char* Ap /*NAT [i][k] k-minor*/, const c
                         if (i < I && j2 < J2) atomicAdd(&C2[(long)i * J2 + j2], o[r]);
                     }
                 }
+            }
         }
     }
 }

@@ -152,10 +152,12 @@ static __device__ __forceinline__ float erf_fast(float x) {
 static __device__ __forceinline__ float gelu_f(float x) {
     return 0.5f * x * (1.0f + erf_fast(x * 0.70710678118654752f));
 }
+// exp(-x^2 / 2) as gelu_grad_f evaluates it (m2m_gelu_table_probe form 4 measures it on its own)
+static __device__ __forceinline__ float gelu_exp_f(float x) { return __expf(-0.5f * x * x); }
 // gelu(x) and d gelu / dx = Phi(x) + x phi(x)
 static __device__ __forceinline__ void gelu_grad_f(float x, float& g, float& dg) {
     const float cdf = 0.5f * (1.0f + erf_fast(x * 0.70710678118654752f));
-    const float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);
+    const float pdf = 0.3989422804014327f * gelu_exp_f(x);
     g = x * cdf;
     dg = __builtin_fmaf(x, pdf, cdf);
 }

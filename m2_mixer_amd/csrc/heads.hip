@@ -269,8 +269,12 @@ static int heads_samples_per_wg(int B) { return B <= 64 ? 4 : HEAD_S; }
 template <bool BCE>
 static int launch_heads(const m2m_head* heads, int nheads, const void* labels, const float* pos_weight, int B, int D, int K,
                         float* logits, float* losses, int32_t* preds, int zero_losses, const float* weights, void* stream) {
-    if (!heads || nheads < 1 || nheads > HEAD_MAXH || K < 2 || K > HEAD_MAXK || D < 1 || D > 256 || B < 1) {
-        m2m_set_error("heads: unsupported (nheads<=4, K<=32, D<=256)", __FILE__, __LINE__);
+    if (!heads || nheads < 1 || nheads > HEAD_MAXH || K < 2 || K > HEAD_MAXK || B < 1) {
+        m2m_set_error("heads: unsupported (1..4 heads, K in 2..32, B >= 1)", __FILE__, __LINE__);
+        return -1;
+    }
+    if (D != 32 && D != 64 && D != 128 && D != 256) {      // before anything is launched (the losses' zero fill below)
+        m2m_set_error("heads: hidden_dim must be 32, 64, 128 or 256", __FILE__, __LINE__);
         return -1;
     }
     HeadArgs ha;

@@ -293,7 +293,7 @@ def adam_step(param: Tensor, grad: Tensor, m: Tensor, v: Tensor, step: int, lr: 
 # --------------------------------------------------------------------------
 def avmnist_train_step(image, audio, labels, params: Params, cfg: dict, opt_state: dict,
                        lr: float, drop_p: float = 0.0, masks=None,
-                       betas=(0.9, 0.999), eps=1e-8) -> Dict[str, Tensor]:
+                       betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0) -> Dict[str, Tensor]:
     """forward (avmnist_forward) + backward (autograd over the restated forward) +
     Adam on every parameter; mutates `params` and `opt_state` in place."""
     leaves = {k: v.detach().clone().requires_grad_(True) for k, v in params.items()}
@@ -306,7 +306,7 @@ def avmnist_train_step(image, audio, labels, params: Params, cfg: dict, opt_stat
         grads[k] = g
         m = opt_state.setdefault("m", {}).setdefault(k, torch.zeros_like(g))
         v = opt_state.setdefault("v", {}).setdefault(k, torch.zeros_like(g))
-        newp, m2, v2 = adam_step(params[k], g, m, v, opt_state["step"], lr, betas[0], betas[1], eps)
+        newp, m2, v2 = adam_step(params[k], g, m, v, opt_state["step"], lr, betas[0], betas[1], eps, weight_decay)
         params[k] = newp.detach()
         opt_state["m"][k], opt_state["v"][k] = m2, v2
     out = {k: (v.detach() if isinstance(v, Tensor) else v) for k, v in out.items()}
