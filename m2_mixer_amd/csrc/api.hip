@@ -1,5 +1,5 @@
 // Library plumbing, operand packing, Adam, and the small probe kernels used by the tests.
-#include "tile.h"
+#include "dispatch.h"
 #include <stdio.h>
 #include <string.h>
 #include <algorithm>
@@ -318,7 +318,7 @@ extern "C" int m2m_pack_all(const m2m_tower* const* towers, int ntowers, const m
     PackAllArgs a;
     memset(&a, 0, sizeof(a));
     a.nt = ntowers; a.ne = nembeds;
-    static const int pack_nt = [] { const char* e = getenv("M2M_PACK_NT"); return e ? atoi(e) : M2M_PACK_NT_DEFAULT; }();
+    static const int pack_nt = m2m_env_int("M2M_PACK_NT", M2M_PACK_NT_DEFAULT);
     a.nt_loads = pack_nt;
     int prec = -1, tiles = 0, maxD = 0;
     for (int i = 0; i < M2M_PACK_TOWERS; ++i) {
@@ -349,18 +349,9 @@ extern "C" int m2m_pack_all(const m2m_tower* const* towers, int ntowers, const m
     }
     const size_t lds = (size_t)(32 * (maxD + 1) + maxD * 33) * sizeof(float);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    static size_t attr_lds[2] = {0, 0};
-    const int pi = prec == PREC_BF16 ? 0 : 1;
-    if (lds > attr_lds[pi]) {
-        const void* fn = prec == PREC_BF16 ? reinterpret_cast<const void*>(pack_all_kernel<PREC_BF16>) : reinterpret_cast<const void*>(pack_all_kernel<PREC_F32>);
-        M2M_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds[pi] = lds;
-    }
     const dim3 grid((unsigned)(tiles + embed_wgs));
-    if (prec == PREC_BF16) hipLaunchKernelGGL(pack_all_kernel<PREC_BF16>, grid, dim3(256), lds, st, a);
-    else hipLaunchKernelGGL(pack_all_kernel<PREC_F32>, grid, dim3(256), lds, st, a);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    if (prec == PREC_BF16) return m2m_launch<pack_all_kernel<PREC_BF16>>(grid, dim3(256), lds, lds, st, a);
+    return m2m_launch<pack_all_kernel<PREC_F32>>(grid, dim3(256), lds, lds, st, a);
 }
 
 extern "C" int m2m_pack_embed(const m2m_embed* e, void* stream) {
@@ -494,7 +485,7 @@ static int adam_launch(float* param, float* grad, const void* grad_bf16, float* 
     auto launch = [&](float* p_, float* g_, const unsigned short* gb_, float* m_, float* v_, long n_, const AdamRanges& r_) {
         long grid = ceil_div(n_, 1024);
         if (grid > 2048) grid = 2048;
-        static const int nt = [] { const char* e = getenv("M2M_ADAM_NT"); return e ? atoi(e) : M2M_ADAM_NT_DEFAULT; }();
+        static const int nt = m2m_env_int("M2M_ADAM_NT", M2M_ADAM_NT_DEFAULT);
 #define M2M_ADAM_GO(LP, N) hipLaunchKernelGGL((adam_kernel<LP, N>), dim3((unsigned)grid), dim3(256), 0, st, p_, g_, gb_, m_, v_, n_, state, beta1, beta2, \
                                               eps, weight_decay, grad_scale, r_)
 #define M2M_ADAM_SW(LP) switch (nt) { case 1: M2M_ADAM_GO(LP, 1); break; case 3: M2M_ADAM_GO(LP, 3); break; case 7: M2M_ADAM_GO(LP, 7); break; \
@@ -970,10 +961,6 @@ __global__ __launch_bounds__(256, (DK == 64 || DK == 128) ? 4 : 1) void adam_pac
 // Fills `plan_host` (sizeof == m2m_adam_pack_plan_bytes()) for the given model; the caller copies it to device memory and
 // passes that copy to m2m_adam_pack_all.  grad_bf16 != NULL: gradient values come from that bf16 copy of `grad`.
 extern "C" int64_t m2m_adam_pack_plan_bytes(void) { return (int64_t)sizeof(AdamPackPlan); }
-extern "C" int m2m_adam_pack_plan_ranges(const m2m_tower* const* towers, int ntowers, const m2m_embed* const* embeds, int nembeds,
-                                  float* param, float* grad, const void* grad_bf16, float* exp_avg, float* exp_avg_sq, int64_t n,
-                                  const float* state, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
-                                  const m2m_grad_range* ranges, int nranges, void* plan_host);
 extern "C" int m2m_adam_pack_plan(const m2m_tower* const* towers, int ntowers, const m2m_embed* const* embeds, int nembeds,
                                   float* param, float* grad, const void* grad_bf16, float* exp_avg, float* exp_avg_sq, int64_t n,
                                   const float* state, float beta1, float beta2, float eps, float weight_decay, float grad_scale,
@@ -1059,8 +1046,7 @@ extern "C" int m2m_adam_pack_all(const m2m_tower* const* towers, int ntowers, co
             if (towers[i]->prec != prec) { m2m_set_error("adam_pack_all: one precision per launch", __FILE__, __LINE__); return -1; }
             a.tw[i] = m2m_shrink(towers[i]);
             a.skip_w1tc[i] = pack_skips_w1tc(towers[i]);
-            const char* rt_env = getenv("M2M_AP_ROWTILES");       // (read per call: the tests switch it inside one process)
-            const int rowtiles = rt_env ? atoi(rt_env) : 1;
+            const int rowtiles = m2m_env_int("M2M_AP_ROWTILES", 1);       // (read per call: the tests switch it inside one process)
             if (rowtiles && prec == PREC_BF16 && towers[i]->Cp >= AP_W) {      // (narrow towers keep the column-group tiles)
                 a.rowtiles[i] = (int)ceil_div((long)towers[i]->Cp, AP_W);
                 tiles += towers[i]->nblocks * (towers[i]->Cp / 32 + (towers[i]->D / 8) * a.rowtiles[i]);
@@ -1090,39 +1076,25 @@ extern "C" int m2m_adam_pack_all(const m2m_tower* const* towers, int ntowers, co
     const bool lowp = ph->gb != nullptr;
     // the two moment streams past the memory-side cache for models it cannot hold anyway (> 4 M parameters: 64+ MB of moments);
     // small models keep them plain (they stay resident from step to step).  M2M_ADAM_NT=0 / 1 forces either.
-    static const int nt_env = [] { const char* e = getenv("M2M_ADAM_NT"); return e ? atoi(e) : -1; }();
+    static const int nt_env = m2m_env_int("M2M_ADAM_NT", -1);
     long n_own = 0;
     for (int i = 0; i < ntowers; ++i) n_own += 2L * towers[i]->nblocks * towers[i]->C * towers[i]->D;
     const bool ntmv = nt_env >= 0 ? (nt_env & 1) != 0 : n_own > 4000000L;
     const dim3 grid((unsigned)(tiles + embed_wgs + flat_wgs));
     const AdamPackPlan* pd = reinterpret_cast<const AdamPackPlan*>(plan_dev);
-    static size_t attr_lds[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int dk = towers[0]->D;                                  // one hidden_dim for the whole launch: the instantiation built for it
     for (int i = 1; i < ntowers; ++i) if (towers[i]->D != dk) dk = 0;
     if (dk != 64 && dk != 128 && dk != 256) dk = 0;
-#define M2M_APA_GO(PP, LP, NT, slot_)                                                                                                         \
-    do {                                                                                                                                      \
-        auto kern = dk == 128 ? adam_pack_all_kernel<PP, LP, NT, 128> : dk == 256 ? adam_pack_all_kernel<PP, LP, NT, 256>                     \
-                  : dk == 64 ? adam_pack_all_kernel<PP, LP, NT, 64> : adam_pack_all_kernel<PP, LP, NT, 0>;                                   \
-        static size_t attr_lds_k[4] = {0, 0, 0, 0};                                                                                           \
-        size_t& attr_ref = attr_lds_k[dk == 128 ? 1 : dk == 256 ? 2 : dk == 64 ? 3 : 0];                                                       \
-        (void)attr_lds;                                                                                                                       \
-        if (lds > attr_ref) {                                                                                                                 \
-            M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));    \
-            attr_ref = lds;                                                                                                                   \
-        }                                                                                                                                     \
-        hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, a, pd, embed_wgs);                                                                 \
-    } while (0)
-    if (prec == PREC_BF16) {
-        if (lowp) { if (ntmv) M2M_APA_GO(PREC_BF16, true, true, 0); else M2M_APA_GO(PREC_BF16, true, false, 1); }
-        else { if (ntmv) M2M_APA_GO(PREC_BF16, false, true, 2); else M2M_APA_GO(PREC_BF16, false, false, 3); }
-    } else {
-        if (lowp) { if (ntmv) M2M_APA_GO(PREC_F32, true, true, 4); else M2M_APA_GO(PREC_F32, true, false, 5); }
-        else { if (ntmv) M2M_APA_GO(PREC_F32, false, true, 6); else M2M_APA_GO(PREC_F32, false, false, 7); }
-    }
-#undef M2M_APA_GO
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    // (precision, bf16 gradient copy, non-temporal moments, hidden_dim the kernel is specialised for: 0 = any)
+    return m2m_dispatch(m2m_precs{}, prec, -1, [&](auto P) {
+        return m2m_dispatch<0, 1>(lowp, -1, [&](auto LP) {
+            return m2m_dispatch<0, 1>(ntmv, -1, [&](auto NT) {
+                return m2m_dispatch<0, 64, 128, 256>(dk, -1, [&](auto DK) {
+                    return m2m_launch<adam_pack_all_kernel<P(), LP() != 0, NT() != 0, DK()>>(grid, dim3(256), lds, lds, st, a, pd, embed_wgs);
+                });
+            });
+        });
+    });
 }
 
 // One tiny launch at the head of a training step instead of three scattered through it (each tiny kernel costs
@@ -1135,16 +1107,12 @@ __global__ void step_prologue_kernel(float* adam_state, unsigned int* drop_count
 }
 extern "C" int m2m_step_prologue(float* adam_state, uint32_t* drop_counter, float* losses, int nlosses, void* stream) {
     if (nlosses < 0 || nlosses > 64) { m2m_set_error("step_prologue: nlosses must be in [0, 64]", __FILE__, __LINE__); return -1; }
-    hipLaunchKernelGGL(step_prologue_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), adam_state, drop_counter, losses, nlosses);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<step_prologue_kernel>(dim3(1), dim3(64), 0, 0, reinterpret_cast<hipStream_t>(stream), adam_state, drop_counter, losses, nlosses);
 }
 
 __global__ void counter_add_kernel(unsigned int* c, unsigned int d) { *c += d; }
 extern "C" int m2m_counter_add(uint32_t* counter, uint32_t delta, void* stream) {
-    hipLaunchKernelGGL(counter_add_kernel, dim3(1), dim3(1), 0, reinterpret_cast<hipStream_t>(stream), counter, delta);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<counter_add_kernel>(dim3(1), dim3(1), 0, 0, reinterpret_cast<hipStream_t>(stream), counter, delta);
 }
 
 // ---------------------------------------------------------------------------------------------------

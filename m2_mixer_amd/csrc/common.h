@@ -15,6 +15,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 #define M2M_WAVE 64
 
@@ -397,7 +398,14 @@ static __device__ __forceinline__ float lane_class_sum(float v, int stride) {
         if (_e != hipSuccess) { m2m_set_error(hipGetErrorString(_e), __FILE__, __LINE__); return -2; } \
     } while (0)
 
-void m2m_set_error(const char* msg, const char* file, int line);
+// (m2m_set_error: host.h)
+
+// Integer environment switch (unset: dflt).  A switch that is read once per process keeps the result in a `static const` at its
+// site; one that the tests flip inside a process is read on every call.
+static inline int m2m_env_int(const char* name, int dflt) {
+    const char* e = getenv(name);
+    return e ? atoi(e) : dflt;
+}
 
 // ---- optional phase timers (diagnostic build only: make TIMERS=1 -> libm2mixer_timers.so) -------------
 // Workgroup 0 / thread 0 accumulates the 100 MHz wall clock spent between consecutive marks of a launch.

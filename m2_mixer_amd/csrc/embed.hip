@@ -11,6 +11,7 @@
 #include "embed_wgrad.h"
 
 #include "embed_fwd.h"
+#include "dispatch.h"
 
 template <int P, int D, int RB>
 __global__ __launch_bounds__(NTHREADS) void embed_fwd_kernel(const m2m_embed em, const float* __restrict__ in, long M, int N,
@@ -113,12 +114,8 @@ static int launch_embed_fwd(const m2m_embed* e, const float* in, int B, float* x
     // the step's critical path, and 64 workgroups of 32 rows left three quarters of the chip idle
     constexpr int RB = 16;
     const size_t lds = (size_t)RB * EMB_LD * 4 + (size_t)RB * EMB_KS * Prec<P>::ESZ + EMB_KMAX * 4 + RB * 8;
-    auto kern = embed_fwd_kernel<P, D, RB>;
-    static bool done = false;
-    if (!done) { M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done = true; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)((M + RB - 1) / RB)), dim3(NTHREADS), lds, st, *e, in, M, N, x0, (int)embed_fwd_fast_ok(e, in), hd);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<embed_fwd_kernel<P, D, RB>>(dim3((unsigned)((M + RB - 1) / RB)), dim3(NTHREADS), lds, lds, st, *e, in, M, N, x0,
+                                                  (int)embed_fwd_fast_ok(e, in), hd);
 }
 template <int P, int D>
 static int launch_embed_fwd_group(const m2m_embed* const* es, const float* const* ins, float* const* x0s, const int* nsplits,
@@ -148,36 +145,21 @@ static int launch_embed_fwd_group(const m2m_embed* const* es, const float* const
         total += nwg;
     }
     const size_t lds = (size_t)RB * EMB_LD * 4 + (size_t)RB * EMB_KS * Prec<P>::ESZ + EMB_KMAX * 4 + RB * 8;
-    auto kern = embed_fwd_group_kernel<P, D, RB>;
-    static bool done = false;
-    if (!done) { M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done = true; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(NTHREADS), lds, st, a);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<embed_fwd_group_kernel<P, D, RB>>(dim3((unsigned)total), dim3(NTHREADS), lds, lds, st, a);
 }
 
 template <int P, int D>
 static int launch_embed_wgrad(const m2m_embed* e, const float* in, const float* dx0, int B, hipStream_t st) {
     const EmbedWgradPlan pl = embed_wgrad_plan(e, B, 256);
     const size_t lds = embed_wgrad_lds<D, P>();
-    auto kern = embed_wgrad_kernel<P, D>;
-    static bool done = false;
-    if (!done) { M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done = true; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)pl.nchunks, (unsigned)pl.groups), dim3(NTHREADS), lds, st, *e, in, dx0, pl.M, pl.N, pl.tpg);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<embed_wgrad_kernel<P, D>>(dim3((unsigned)pl.nchunks, (unsigned)pl.groups), dim3(NTHREADS), lds, lds, st, *e, in, dx0, pl.M, pl.N, pl.tpg);
 }
 template <int P, int D>
 static int launch_embed_wgrad_group(const m2m_embed* const* es, const float* const* ins, const float* const* dx0s, int B, hipStream_t st) {
     EmbedWgradGroupArgs a;
     const int total = embed_wgrad_group_args(a, es, ins, dx0s, B, 256);
     const size_t lds = embed_wgrad_lds<D, P>();
-    auto kern = embed_wgrad_group_kernel<P, D>;
-    static bool done = false;
-    if (!done) { M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done = true; }
-    hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(NTHREADS), lds, st, a);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<embed_wgrad_group_kernel<P, D>>(dim3((unsigned)total), dim3(NTHREADS), lds, lds, st, a);
 }
 
 extern "C" int m2m_embed_forward(const m2m_embed* e, const float* input, int B, float* x0, void* stream) {
@@ -186,10 +168,8 @@ extern "C" int m2m_embed_forward(const m2m_embed* e, const float* input, int B, 
 extern "C" int m2m_embed_forward_head(const m2m_embed* e, const float* input, int B, float* x0, const m2m_step_head* head, void* stream) {
     if (int rc = m2m_check_embed(e, B)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define M2M_EF_CASE(PP, DD) if (e->prec == PP && e->D == DD) return launch_embed_fwd<PP, DD>(e, input, B, x0, st, head);
-    M2M_EF_CASE(PREC_BF16, 32) M2M_EF_CASE(PREC_BF16, 64) M2M_EF_CASE(PREC_BF16, 128) M2M_EF_CASE(PREC_BF16, 256)
-    M2M_EF_CASE(PREC_F32, 32) M2M_EF_CASE(PREC_F32, 64) M2M_EF_CASE(PREC_F32, 128) M2M_EF_CASE(PREC_F32, 256)
-#undef M2M_EF_CASE
+    const int rc = m2m_dispatch_pd(m2m_wide_dims{}, e->prec, e->D, [&](auto P, auto D) { return launch_embed_fwd<P(), D()>(e, input, B, x0, st, head); });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("embed_forward: unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }
@@ -197,10 +177,8 @@ extern "C" int m2m_embed_forward_head(const m2m_embed* e, const float* input, in
 extern "C" int m2m_embed_wgrad(const m2m_embed* e, const float* input, const float* d_x0, int B, void* stream) {
     if (int rc = m2m_check_embed(e, B)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-#define M2M_EW_CASE(PP, DD) if (e->prec == PP && e->D == DD) return launch_embed_wgrad<PP, DD>(e, input, d_x0, B, st);
-    M2M_EW_CASE(PREC_BF16, 32) M2M_EW_CASE(PREC_BF16, 64) M2M_EW_CASE(PREC_BF16, 128) M2M_EW_CASE(PREC_BF16, 256)
-    M2M_EW_CASE(PREC_F32, 32) M2M_EW_CASE(PREC_F32, 64) M2M_EW_CASE(PREC_F32, 128) M2M_EW_CASE(PREC_F32, 256)
-#undef M2M_EW_CASE
+    const int rc = m2m_dispatch_pd(m2m_wide_dims{}, e->prec, e->D, [&](auto P, auto D) { return launch_embed_wgrad<P(), D()>(e, input, d_x0, B, st); });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("embed_wgrad: unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }
@@ -217,10 +195,8 @@ extern "C" int m2m_embeds_wgrad(const m2m_embed* const* embeds, const float* con
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const m2m_embed* e = embeds[0];
-#define M2M_EWG_CASE(PP, DD) if (e->prec == PP && e->D == DD) return launch_embed_wgrad_group<PP, DD>(embeds, inputs, d_x0s, B, st);
-    M2M_EWG_CASE(PREC_BF16, 32) M2M_EWG_CASE(PREC_BF16, 64) M2M_EWG_CASE(PREC_BF16, 128) M2M_EWG_CASE(PREC_BF16, 256)
-    M2M_EWG_CASE(PREC_F32, 32) M2M_EWG_CASE(PREC_F32, 64) M2M_EWG_CASE(PREC_F32, 128) M2M_EWG_CASE(PREC_F32, 256)
-#undef M2M_EWG_CASE
+    const int rc = m2m_dispatch_pd(m2m_wide_dims{}, e->prec, e->D, [&](auto P, auto D) { return launch_embed_wgrad_group<P(), D()>(embeds, inputs, d_x0s, B, st); });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("embeds_wgrad: unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }
@@ -229,7 +205,7 @@ extern "C" int m2m_embeds_wgrad(const m2m_embed* const* embeds, const float* con
 // enough for the weight stream to dominate (the audio spectrogram patches), else 1.
 extern "C" int m2m_embed_fwd_splits(const m2m_embed* e) {
     if (!e) return 1;
-    static const int forced = [] { const char* v = getenv("M2M_EMBED_SPLITS"); return v ? atoi(v) : 0; }();    // diagnostic (1..4)
+    static const int forced = m2m_env_int("M2M_EMBED_SPLITS", 0);    // diagnostic (1..4)
     const bool pays = embed_fwd_fast_ok(e, nullptr) && e->Kp >= 4 * EMB_FKS;
     if (pays && forced >= 1 && forced <= 4) return forced;
     return pays ? 2 : 1;
@@ -247,10 +223,8 @@ extern "C" int m2m_embeds_forward(const m2m_embed* const* embeds, const float* c
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const m2m_embed* e = embeds[0];
-#define M2M_EFG_CASE(PP, DD) if (e->prec == PP && e->D == DD) return launch_embed_fwd_group<PP, DD>(embeds, inputs, x0s, nsplits, part_strides, head, B, st);
-    M2M_EFG_CASE(PREC_BF16, 32) M2M_EFG_CASE(PREC_BF16, 64) M2M_EFG_CASE(PREC_BF16, 128) M2M_EFG_CASE(PREC_BF16, 256)
-    M2M_EFG_CASE(PREC_F32, 32) M2M_EFG_CASE(PREC_F32, 64) M2M_EFG_CASE(PREC_F32, 128) M2M_EFG_CASE(PREC_F32, 256)
-#undef M2M_EFG_CASE
+    const int rc = m2m_dispatch_pd(m2m_wide_dims{}, e->prec, e->D, [&](auto P, auto D) { return launch_embed_fwd_group<P(), D()>(embeds, inputs, x0s, nsplits, part_strides, head, B, st); });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("embeds_forward: unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }

@@ -1,12 +1,9 @@
 // Patch-embedding weight gradient: the workgroup body, shared by embed.hip (its own launches, 512 threads) and
 // tower_wgrad.hip (as extra workgroups of the merged weight-gradient launch, 256 threads).
 #pragma once
-#include "tile.h"
-#include <stdlib.h>
+#include "host.h"
 
 #define EBM 32             // token rows per tile
-
-int m2m_check_embed(const m2m_embed* e, int B);    // embed.hip
 
 struct PatchGeom {
     int Cin, H, W, ph, pw, GW, N, K;
@@ -153,7 +150,6 @@ static __device__ __forceinline__ void embed_wgrad_body(const m2m_embed& em, con
 // group and row.  Reference: the weight gradient of MLPMixer.to_patch_embedding (modules/mixer.py:143-146) under autograd.
 #define EFK 32
 template <int D, int NT> static constexpr size_t embed_wgrad_fast_red_bytes() { return (size_t)(NT / 64) * (EFK / 16) * (D / 16) * 64 * 16; }
-bool m2m_split_eligible(const m2m_tower* t, int B, int training);    // split_api.hip (its backward does not write the image)
 template <int D, int NT>
 static __device__ __forceinline__ void embed_wgrad_fast_body(const m2m_embed& em, const float* __restrict__ in,
                                                              const char* __restrict__ dx0_chn, long M, int N, int npairs, int rpt,
@@ -366,7 +362,7 @@ static inline int embed_wgrad_group_args_fast(EmbedWgradGroupArgs& a, const m2m_
         a.M[i] = (long)B * N; a.N[i] = N; a.npairs[i] = (nchain * BM + WPAIR - 1) / WPAIR; a.rpt[i] = SPW * t->N;
         a.nchunks[i] = (e->K + EFK - 1) / EFK; a.groups[i] = 1; a.tpg[i] = 0;
         // 8-byte gathers: every address the kernel forms is even (patch rows, token origins, channel / sample strides, K)
-        static const int vec2_on = [] { const char* v = getenv("M2M_EMBED_VEC2"); return v ? atoi(v) : 1; }();
+        static const int vec2_on = m2m_env_int("M2M_EMBED_VEC2", 1);
         a.vec2[i] = (vec2_on && e->pw % 2 == 0 && e->W % 2 == 0 && ((long)e->H * e->W) % 2 == 0 && e->K % 2 == 0 && ((uintptr_t)ins[i] & 7) == 0) ? 1 : 0;
         total += a.nchunks[i];
     }

@@ -8,8 +8,7 @@
 // re-pack need no packed image of them.  tanh(W1 a + b1), tanh(W2 b + b2) and z are saved by a training forward; the backward
 // reads them instead of recomputing three products.  Its weight gradients are per-workgroup partial sums over fixed row chunks,
 // added in chunk order by a second launch (no float atomics: a bf16 step stays bit-reproducible).
-#include "common.h"
-#include "../../include/m2mixer.h"
+#include "host.h"
 
 #define FUS_THREADS 256
 // rows per thread of the forward / backward tiles (template argument GATE_RPT): 16, or 4 where 16 would leave the chip

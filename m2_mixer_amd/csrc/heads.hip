@@ -7,7 +7,7 @@
 // own whole samples (the wide path), computed here from the tower output (m2m_head.tokens).
 // BCE = true is the MM-IMDb variant (models/mmimdb.py:47-50, :115-133): nn.BCEWithLogitsLoss(pos_weight) with mean
 // reduction over all B*K elements per head, preds = sigmoid(logits) > 0.5 per label.
-#include "tile.h"
+#include "dispatch.h"
 
 #ifndef HEAD_S
 #define HEAD_S 16       // samples per workgroup (small: the launch sits between forward and backward on the critical path)
@@ -246,21 +246,16 @@ template <bool BCE, int S, int DD>
 static int launch_heads_sd(const HeadArgs& ha, int nheads, const void* labels, const float* pos_weight, int B, int K,
                            float* logits, float* losses, int32_t* preds, hipStream_t st) {
     const size_t lds = sizeof(float) * ((size_t)S * (DD + 4) + (size_t)HEAD_MAXK * (DD + 4) + 2 * S * HEAD_MAXK + S);
-    static bool done = false;
-    if (!done) { M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(heads_kernel<BCE, S, DD>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024)); done = true; }
-    hipLaunchKernelGGL((heads_kernel<BCE, S, DD>), dim3((B + S - 1) / S, nheads), dim3(NTHREADS), lds, st, ha, labels, pos_weight, B, DD, K, logits, losses, preds, nheads);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<heads_kernel<BCE, S, DD>>(dim3((B + S - 1) / S, nheads), dim3(NTHREADS), lds, 160 * 1024, st, ha, labels, pos_weight, B, DD, K, logits,
+                                                losses, preds, nheads);
 }
 template <bool BCE, int S>
 static int launch_heads_s(const HeadArgs& ha, int nheads, const void* labels, const float* pos_weight, int B, int D, int K,
                           float* logits, float* losses, int32_t* preds, hipStream_t st) {
-    switch (D) {
-        case 32:  return launch_heads_sd<BCE, S, 32>(ha, nheads, labels, pos_weight, B, K, logits, losses, preds, st);
-        case 64:  return launch_heads_sd<BCE, S, 64>(ha, nheads, labels, pos_weight, B, K, logits, losses, preds, st);
-        case 128: return launch_heads_sd<BCE, S, 128>(ha, nheads, labels, pos_weight, B, K, logits, losses, preds, st);
-        case 256: return launch_heads_sd<BCE, S, 256>(ha, nheads, labels, pos_weight, B, K, logits, losses, preds, st);
-    }
+    const int rc = m2m_dispatch(m2m_wide_dims{}, D, M2M_NO_BUILD, [&](auto DD) {
+        return launch_heads_sd<BCE, S, DD()>(ha, nheads, labels, pos_weight, B, K, logits, losses, preds, st);
+    });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("heads: hidden_dim must be 32, 64, 128 or 256", __FILE__, __LINE__);
     return -1;
 }

@@ -6,6 +6,7 @@
 // beside them.  Backward needs no mask regeneration: the saved layer output is relu(z) * keep * scale, which is
 // non-zero exactly where the gradient passes, so dz = d_out * scale * [out != 0].
 #include "mlp_body.h"
+#include "dispatch.h"
 
 template <int MLP_S, int MLP_T>
 __global__ __launch_bounds__(MLP_T) void mlp_fwd_kernel(const m2m_mlp m, const float* __restrict__ x, int B, float* __restrict__ out,
@@ -229,23 +230,13 @@ template <int S, int T>
 static int launch_mlp_fwd(const m2m_mlp* m, const float* x, int B, float* out, long out_ss, float* out_dense, int training,
                           unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st) {
     const size_t lds = sizeof(float) * ((size_t)2 * S * (MLP_MAXW + 1) + (size_t)MLP_MAXW * (MLP_MAXW + 1));
-    auto kern = mlp_fwd_kernel<S, T>;
-    static bool done = false;
-    if (!done) { M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done = true; }
-    hipLaunchKernelGGL(kern, dim3((B + S - 1) / S), dim3(T), lds, st, *m, x, B, out, out_ss, out_dense, training, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<mlp_fwd_kernel<S, T>>(dim3((B + S - 1) / S), dim3(T), lds, lds, st, *m, x, B, out, out_ss, out_dense, training, seed, step, step_dev);
 }
 template <int S, int T>
 static int launch_mlp_bwd(const m2m_mlp* m, const float* x, int B, const float* d_out, long d_out_ss, const float* d_out_dense,
                           hipStream_t st) {
     const size_t lds = sizeof(float) * ((size_t)3 * S * (MLP_MAXW + 1) + (size_t)MLP_MAXW * (MLP_MAXW + 1));
-    auto kern = mlp_bwd_kernel<S, T>;
-    static bool done = false;
-    if (!done) { M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done = true; }
-    hipLaunchKernelGGL(kern, dim3((B + S - 1) / S), dim3(T), lds, st, *m, x, B, d_out, d_out_ss, d_out_dense);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<mlp_bwd_kernel<S, T>>(dim3((B + S - 1) / S), dim3(T), lds, lds, st, *m, x, B, d_out, d_out_ss, d_out_dense);
 }
 #define MLP_SMALL_BATCH 2048      // up to here the MFMA kernels (one 16-sample tile per workgroup)
 
@@ -255,12 +246,8 @@ extern "C" int m2m_mlp_forward(const m2m_mlp* m, const float* x, int B, float* o
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (B <= MLP_SMALL_BATCH) {
         const size_t lds = sizeof(float) * ((size_t)2 * MLPM_S + MLP_MAXW) * (MLP_MAXW + 1);
-        static bool done = false;
-        if (!done) { M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_fwd_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done = true; }
-        hipLaunchKernelGGL(mlp_fwd_mfma_kernel, dim3((B + MLPM_S - 1) / MLPM_S), dim3(MLPM_T), lds, st, *m, x, B, out, (long)out_sample_stride,
-                           out_dense, training, seed, step, step_dev);
-        M2M_CHECK_HIP(hipGetLastError());
-        return 0;
+        return m2m_launch<mlp_fwd_mfma_kernel>(dim3((B + MLPM_S - 1) / MLPM_S), dim3(MLPM_T), lds, lds, st, *m, x, B, out, (long)out_sample_stride,
+                                               out_dense, training, seed, step, step_dev);
     }
     return launch_mlp_fwd<32, 256>(m, x, B, out, (long)out_sample_stride, out_dense, training, seed, step, step_dev, st);
 }
@@ -271,11 +258,7 @@ extern "C" int m2m_mlp_backward(const m2m_mlp* m, const float* x, int B, const f
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (B <= MLP_SMALL_BATCH) {
         const size_t lds = sizeof(float) * ((size_t)3 * MLPM_S + MLP_MAXW) * (MLP_MAXW + 1);
-        static bool done = false;
-        if (!done) { M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_bwd_mfma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); done = true; }
-        hipLaunchKernelGGL(mlp_bwd_mfma_kernel, dim3((B + MLPM_S - 1) / MLPM_S), dim3(MLPM_T), lds, st, *m, x, B, d_out, (long)d_out_sample_stride, d_out_dense);
-        M2M_CHECK_HIP(hipGetLastError());
-        return 0;
+        return m2m_launch<mlp_bwd_mfma_kernel>(dim3((B + MLPM_S - 1) / MLPM_S), dim3(MLPM_T), lds, lds, st, *m, x, B, d_out, (long)d_out_sample_stride, d_out_dense);
     }
     return launch_mlp_bwd<32, 256>(m, x, B, d_out, (long)d_out_sample_stride, d_out_dense, st);
 }

@@ -8,8 +8,7 @@
 //
 // A workgroup histograms its rows in LDS (32-bit LDS atomics) and then issues ONE 64-bit global atomic add per non-zero cell:
 // a 512-row batch costs tens of global atomics.  No float atomics.
-#include "common.h"
-#include "../../include/m2mixer.h"
+#include "host.h"
 
 #define SC_THREADS 256
 #define SC_ROWS_PER_WG 1024                                  // multiclass rows of one workgroup (4 per thread)

@@ -178,9 +178,3 @@ static __device__ __forceinline__ void split_small_grads_body(const SplitReduceT
     }
 }
 #define SPR_NBX ((SPP_STRIDE + SPR_COLS - 1) / SPR_COLS)        // workgroups per (tower, slot set)
-
-// tower_bwd.hip: fills `x` for the slot reduction of tower t's fused single-tower backward launch at batch B; returns false if
-// that launch does not use slots.  (The caller reduces: immediately, or inside the next weight-gradient launch when the tower's
-// wgrad_flags carry M2M_WGRAD_REDUCES_SMALL.)
-bool m2m_small_part_deferred(SplitReduceTower& x, const m2m_tower* t, int B);
-int m2m_split_small_grads(const SplitReduceArgs& a, hipStream_t st);

@@ -1,32 +1,13 @@
 // Host side of the split path: decides when a tower takes it and issues its launch sequence (see split.h).  Entered from
 // m2m_tower(s)_forward / _backward; nothing here is a new C-ABI entry point.
-#include "split.h"
-#include <stdlib.h>
-
-int m2m_split_mix_forward(const SplitMixArgs& a, int D, int training, float p_drop, unsigned int seed, unsigned int step,
-                          const unsigned int* step_dev, hipStream_t st);
-int m2m_split_chain_forward(const SplitChainArgs& a, int D, int training, float p_drop, unsigned int seed, unsigned int step,
-                            const unsigned int* step_dev, hipStream_t st);
-int m2m_split_mix_backward(const SplitMixBwdArgs& a, int D, float p_drop, unsigned int seed, unsigned int step,
-                           const unsigned int* step_dev, hipStream_t st);
-int m2m_split_chain_backward(const SplitChainArgs& a, int D, float p_drop, unsigned int seed, unsigned int step,
-                             const unsigned int* step_dev, hipStream_t st);
-int m2m_split_small_grads(const SplitReduceArgs& a, hipStream_t st);
+#include "host.h"
 
 // Rows (B * N) from which the split path pays: below it the chain launches cannot fill the chip (one workgroup per 128 rows
 // and column split) and the fused one-launch tower wins.  M2M_SPLIT=0 / 1 forces the choice (diagnostics, A/B tests).
-static int split_min_rows() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("M2M_SPLIT_MIN_ROWS");
-        v = e ? atoi(e) : (1 << 30);       // off by default until the measured step beats the fused path (profiles/); M2M_SPLIT=1 forces it
-    }
-    return v;
-}
-static int split_mode() {                       // -1 auto, 0 never, 1 whenever the buffers are there
-    const char* e = getenv("M2M_SPLIT");
-    return e ? atoi(e) : -1;
-}
+// (off by default until the measured step beats the fused path (profiles/); M2M_SPLIT=1 forces it.  Both are read per call:
+// the tests switch M2M_SPLIT inside one process.)
+static int split_min_rows() { return m2m_env_int("M2M_SPLIT_MIN_ROWS", 1 << 30); }
+static int split_mode() { return m2m_env_int("M2M_SPLIT", -1); }      // -1 auto, 0 never, 1 whenever the buffers are there
 
 static int split_count(const m2m_tower* t) {
     int s = t->nsplit < SP_MAX_SPLITS ? t->nsplit : SP_MAX_SPLITS;

@@ -8,7 +8,7 @@
 // 16 B, lane-linear, exactly the DMA's image), double-buffered: the DMA of chunk c + 1 is in flight while chunk c computes
 // (counted vmcnt, raw s_barrier -- a __syncthreads() would drain the DMA).  The activations (A, dYd fragments of the wave's
 // 32 rows) stay in registers for the whole launch.
-#include "split.h"
+#include "dispatch.h"
 
 TIMER_DECL(g_tm_scf);
 TIMER_READER(m2m_debug_timers_scf, g_tm_scf)
@@ -441,15 +441,7 @@ template <int D, int DM>
 static int launch_chain_fwd_dm(const SplitChainArgs& a, int training, unsigned int seed, unsigned int step,
                                const unsigned int* step_dev, hipStream_t st) {
     const size_t lds = chain_fwd_lds<D>();
-    auto kern = split_chain_fwd_kernel<D, DM>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.nsplit * a.ntow * a.max_rt), dim3(SP_THREADS), lds, st, a, training, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<split_chain_fwd_kernel<D, DM>>(dim3(a.nsplit * a.ntow * a.max_rt), dim3(SP_THREADS), lds, lds, st, a, training, seed, step, step_dev);
 }
 
 int m2m_split_chain_forward(const SplitChainArgs& a, int D, int training, float p_drop, unsigned int seed, unsigned int step,
@@ -459,33 +451,17 @@ int m2m_split_chain_forward(const SplitChainArgs& a, int D, int training, float 
         const int per = (a.t[i].nunits + a.nsplit - 1) / a.nsplit;
         if (per > SP_MAX_UNITS_PER_SPLIT || a.t[i].nunits < a.nsplit) { m2m_set_error("split path: channel_dim out of range for the column split", __FILE__, __LINE__); return -1; }
     }
-    switch (m2m_drop_mode(training, p_drop)) {
-        case DM_NONE: return launch_chain_fwd_dm<128, DM_NONE>(a, training, seed, step, step_dev, st);
-        case DM_HALF: return launch_chain_fwd_dm<128, DM_HALF>(a, training, seed, step, step_dev, st);
-        default:      return launch_chain_fwd_dm<128, DM_GEN>(a, training, seed, step, step_dev, st);
-    }
+    return m2m_dispatch_dm(training, p_drop, [&](auto DM) { return launch_chain_fwd_dm<128, DM()>(a, training, seed, step, step_dev, st); });
 }
 
 template <int D, int DM>
 static int launch_chain_bwd_dm(const SplitChainArgs& a, unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st) {
     const size_t lds = chain_bwd_lds<D>();
-    auto kern = split_chain_bwd_kernel<D, DM>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(a.nsplit * a.ntow * a.max_rt), dim3(SP_THREADS), lds, st, a, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<split_chain_bwd_kernel<D, DM>>(dim3(a.nsplit * a.ntow * a.max_rt), dim3(SP_THREADS), lds, lds, st, a, seed, step, step_dev);
 }
 
 int m2m_split_chain_backward(const SplitChainArgs& a, int D, float p_drop, unsigned int seed, unsigned int step,
                              const unsigned int* step_dev, hipStream_t st) {
     if (D != 128) { m2m_set_error("split path: hidden_dim 128 only in this build", __FILE__, __LINE__); return -1; }
-    switch (m2m_drop_mode(1, p_drop)) {
-        case DM_NONE: return launch_chain_bwd_dm<128, DM_NONE>(a, seed, step, step_dev, st);
-        case DM_HALF: return launch_chain_bwd_dm<128, DM_HALF>(a, seed, step, step_dev, st);
-        default:      return launch_chain_bwd_dm<128, DM_GEN>(a, seed, step, step_dev, st);
-    }
+    return m2m_dispatch_dm(1, p_drop, [&](auto DM) { return launch_chain_bwd_dm<128, DM()>(a, seed, step, step_dev, st); });
 }

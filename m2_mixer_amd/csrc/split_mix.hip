@@ -11,7 +11,7 @@
 //   backward mix(b):  g = [b == last: upstream through the final LayerNorm | carry + LN2'(sum_s dAslab_s) of block b+1, then the
 //                     token-mixing backward of block b+1]; carry = g; dYd(b) = dropout mask x g -> db2, operand images
 //                     dy_nat(b) / dyt_chn(b);   after block 0's chain launch: the same without a next block -> d_x0
-#include "split.h"
+#include "dispatch.h"
 
 TIMER_DECL(g_tm_smf);
 TIMER_READER(m2m_debug_timers_smf, g_tm_smf)
@@ -214,30 +214,17 @@ template <int D, int NMAX, int DM>
 static int launch_mix_fwd_dm(const SplitMixArgs& a, int training, unsigned int seed, unsigned int step, const unsigned int* step_dev,
                              hipStream_t st) {
     const size_t lds = mix_fwd_lds<D, NMAX>();
-    auto kern = split_mix_fwd_kernel<D, NMAX, DM>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
     int mx = 0;
     for (int i = 0; i < a.ntow; ++i) mx = a.t[i].ntiles > mx ? a.t[i].ntiles : mx;
-    hipLaunchKernelGGL(kern, dim3(mx, a.ntow), dim3(NTHREADS), lds, st, a, training, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<split_mix_fwd_kernel<D, NMAX, DM>>(dim3(mx, a.ntow), dim3(NTHREADS), lds, lds, st, a, training, seed, step, step_dev);
 }
 
 int m2m_split_mix_forward(const SplitMixArgs& a, int D, int training, float p_drop, unsigned int seed, unsigned int step,
                           const unsigned int* step_dev, hipStream_t st) {
     if (D != 128) { m2m_set_error("split path: hidden_dim 128 only in this build", __FILE__, __LINE__); return -1; }
-    const int dm = m2m_drop_mode(training, p_drop);
-    const bool n4 = a.t[0].N <= 4;
-#define M2M_MIXF(NM, DMV) return launch_mix_fwd_dm<128, NM, DMV>(a, training, seed, step, step_dev, st)
-    if (n4) { if (dm == DM_NONE) M2M_MIXF(4, DM_NONE); if (dm == DM_HALF) M2M_MIXF(4, DM_HALF); M2M_MIXF(4, DM_GEN); }
-    if (dm == DM_NONE) M2M_MIXF(8, DM_NONE);
-    if (dm == DM_HALF) M2M_MIXF(8, DM_HALF);
-    M2M_MIXF(8, DM_GEN);
-#undef M2M_MIXF
+    return m2m_fused_class(a.t[0].N, a.t[0].T, [&](auto NMAX, auto) {
+        return m2m_dispatch_dm(training, p_drop, [&](auto DM) { return launch_mix_fwd_dm<128, NMAX(), DM()>(a, training, seed, step, step_dev, st); });
+    });
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -559,37 +546,21 @@ __global__ __launch_bounds__(SPR_COLS * SPR_GROUPS) void split_small_grads_kerne
 int m2m_split_small_grads(const SplitReduceArgs& a, hipStream_t st) {
     int nl = 0;
     for (int i = 0; i < a.ntow; ++i) nl = a.t[i].nlaunch > nl ? a.t[i].nlaunch : nl;
-    hipLaunchKernelGGL(split_small_grads_kernel, dim3(SPR_NBX, nl, a.ntow), dim3(SPR_COLS * SPR_GROUPS), 0, st, a);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<split_small_grads_kernel>(dim3(SPR_NBX, nl, a.ntow), dim3(SPR_COLS * SPR_GROUPS), 0, 0, st, a);
 }
 
 template <int D, int NMAX, int TG, int DM>
 static int launch_mix_bwd_dm(const SplitMixBwdArgs& a, unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st) {
     const size_t lds = mix_bwd_lds<D, NMAX, TG>();
-    auto kern = split_mix_bwd_kernel<D, NMAX, TG, DM>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
     int mx = 0;
     for (int i = 0; i < a.ntow; ++i) mx = a.t[i].ntiles > mx ? a.t[i].ntiles : mx;
-    hipLaunchKernelGGL(kern, dim3(mx, a.ntow), dim3(NTHREADS), lds, st, a, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<split_mix_bwd_kernel<D, NMAX, TG, DM>>(dim3(mx, a.ntow), dim3(NTHREADS), lds, lds, st, a, seed, step, step_dev);
 }
 
 int m2m_split_mix_backward(const SplitMixBwdArgs& a, int D, float p_drop, unsigned int seed, unsigned int step,
                            const unsigned int* step_dev, hipStream_t st) {
     if (D != 128) { m2m_set_error("split path: hidden_dim 128 only in this build", __FILE__, __LINE__); return -1; }
-    const int dm = m2m_drop_mode(1, p_drop);
-    const int N = a.t[0].N, T = a.t[0].T;
-#define M2M_MIXB(NM, TGV, DMV) return launch_mix_bwd_dm<128, NM, TGV, DMV>(a, seed, step, step_dev, st)
-#define M2M_MIXB_DM(NM, TGV) { if (dm == DM_NONE) M2M_MIXB(NM, TGV, DM_NONE); if (dm == DM_HALF) M2M_MIXB(NM, TGV, DM_HALF); M2M_MIXB(NM, TGV, DM_GEN); }
-    if (N <= 4) M2M_MIXB_DM(4, 8)
-    if (T % 16 == 0) M2M_MIXB_DM(8, 16)
-    M2M_MIXB_DM(8, 8)
-#undef M2M_MIXB_DM
-#undef M2M_MIXB
+    return m2m_fused_class(a.t[0].N, a.t[0].T, [&](auto NMAX, auto TG) {
+        return m2m_dispatch_dm(1, p_drop, [&](auto DM) { return launch_mix_bwd_dm<128, NMAX(), TG(), DM()>(a, seed, step, step_dev, st); });
+    });
 }

@@ -12,6 +12,7 @@
 // The token MLP (N x T, T <= 32) runs on the VALU with the weights broadcast from LDS; h[t] lives in registers.
 #include "tile.h"
 #include "mlp_body.h"
+#include "dispatch.h"
 
 #define TW_COLS 64                 // columns (lanes) per workgroup
 #define TW_TMAX 32                 // token_dim upper bound; the kernels are instantiated for TM = 16 and 32 hidden units (h[] registers,
@@ -24,11 +25,6 @@
 // as it need be -- small launches take 16 waves (8 when token_dim > 16), large ones 4 (more workgroups per CU instead).
 // NC: tokens per chunk of the parameter-gradient reduction (backward): 16 at 4 waves, 8 above (more chunks than waves otherwise)
 template <int NW> struct TokNC { static constexpr int value = NW > 4 ? 8 : 16; };
-
-int m2m_chain_forward_rows(const m2m_tower* t, const float* x0, long x0_ss, int B, float* out, long out_ss, int training,
-                           unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st);
-int m2m_chain_backward_rows(const m2m_tower* t, int B, const float* d_out, long d_out_ss, const float* d_pooled, float* d_x0,
-                            long d_x0_ss, unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st);
 
 // ---- shared prologue: token weights -> LDS, LayerNorm-1 row statistics of this workgroup's samples -------------
 //   w1s[n][t] = W1[t][n], w2s[n][t] = W2[n][t] (t padded to 32 with zeros), b1s[32], b2s[N]
@@ -667,7 +663,7 @@ static m2m_tower block_view(const m2m_tower* t, int b) {
 
 // waves per workgroup of a token launch with `nblk` column blocks (see TokNC above)
 static int tok_waves(int nblk, int TM) {
-    static const int forced = [] { const char* e = getenv("M2M_TOKEN_WAVES"); return e ? atoi(e) : 0; }();   // diagnostic (A/B): 4, 8 or 16
+    static const int forced = m2m_env_int("M2M_TOKEN_WAVES", 0);   // diagnostic (A/B): 4, 8 or 16
     int nw = nblk <= 256 ? 16 : (nblk <= 512 ? 8 : 4);
     if (forced == 4 || forced == 8 || forced == 16) nw = forced;
     if (TM > 16 && nw > 8) nw = 8;                               // 32 hidden units per lane: registers and LDS of 16 waves do not fit
@@ -678,6 +674,9 @@ static int tok_waves(int nblk, int TM) {
 struct MlpRidePending { int kind; MlpRideFwd f; MlpRideBwd b; };
 static thread_local MlpRidePending g_ride = {};
 static size_t mlp_ride_lds(bool bwd) { return sizeof(float) * ((size_t)(bwd ? 3 : 2) * MLPM_S + MLP_MAXW) * (MLP_MAXW + 1); }
+
+// the forward token kernels raise their dynamic-LDS limit only beyond the 48 KiB every kernel may use
+static size_t tok_fwd_lds_attr(size_t lds) { return lds > 48 * 1024 ? lds : 0; }
 
 template <int P, int DM, int TM, int NW>
 static int launch_token_fwd_nw(const m2m_tower* t, int b, const float* src, long src_ss, int B, float* x_mid, float* save_x_in,
@@ -692,27 +691,12 @@ static int launch_token_fwd_nw(const m2m_tower* t, int b, const float* src, long
             g_ride.kind = 0;
             const int n_ride = (r.B + MLPM_S - 1) / MLPM_S;
             const size_t rl = std::max(lds, mlp_ride_lds(false));
-            auto rk = token_fwd_ride_kernel<P, DM, TM>;
-            static size_t ride_attr = 0;
-            if (rl > ride_attr) {
-                M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl));
-                ride_attr = rl;
-            }
-            hipLaunchKernelGGL(rk, dim3(grid + n_ride), dim3(1024), rl, st, *t, b, src, src_ss, B, x_mid, save_x_in, training, seed, step, step_dev,
-                               n_ride, r);
-            M2M_CHECK_HIP(hipGetLastError());
-            return 0;
+            return m2m_launch<token_fwd_ride_kernel<P, DM, TM>>(dim3(grid + n_ride), dim3(1024), rl, rl, st, *t, b, src, src_ss, B, x_mid, save_x_in,
+                                                                training, seed, step, step_dev, n_ride, r);
         }
     }
-    auto kern = token_fwd_kernel<P, DM, TM, NW>;
-    static size_t attr_lds = 48 * 1024;
-    if (lds > attr_lds) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, *t, b, src, src_ss, B, x_mid, save_x_in, training, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<token_fwd_kernel<P, DM, TM, NW>>(dim3(grid), dim3(NW * 64), lds, tok_fwd_lds_attr(lds), st, *t, b, src, src_ss, B, x_mid, save_x_in,
+                                                       training, seed, step, step_dev);
 }
 template <int P, int DM, int TM>
 static int launch_token_fwd(const m2m_tower* t, int b, const float* src, long src_ss, int B, float* x_mid, float* save_x_in,
@@ -748,26 +732,11 @@ static int launch_token_bwd_nw(const m2m_tower* t, int b, const float* g_mid, in
             g_ride.kind = 0;
             const int n_ride = (r.B + MLPM_S - 1) / MLPM_S;
             const size_t rl = std::max(lds, mlp_ride_lds(true));
-            auto rk = token_bwd_cols_ride_kernel<P, DM, TM>;
-            static size_t ride_attr = 0;
-            if (rl > ride_attr) {
-                M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(rk), hipFuncAttributeMaxDynamicSharedMemorySize, (int)rl));
-                ride_attr = rl;
-            }
-            hipLaunchKernelGGL(rk, dim3(grid + n_ride), dim3(1024), rl, st, *t, b, g_mid, B, du, seed, step, step_dev, iters, n_ride, r);
-            M2M_CHECK_HIP(hipGetLastError());
-            return 0;
+            return m2m_launch<token_bwd_cols_ride_kernel<P, DM, TM>>(dim3(grid + n_ride), dim3(1024), rl, rl, st, *t, b, g_mid, B, du, seed, step, step_dev,
+                                                                     iters, n_ride, r);
         }
     }
-    auto kern = token_bwd_cols_kernel<P, DM, TM, NW>;
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NW * 64), lds, st, *t, b, g_mid, B, du, seed, step, step_dev, iters);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<token_bwd_cols_kernel<P, DM, TM, NW>>(dim3(grid), dim3(NW * 64), lds, lds, st, *t, b, g_mid, B, du, seed, step, step_dev, iters);
 }
 template <int P, int DM, int TM>
 static int launch_token_bwd(const m2m_tower* t, int b, const float* g_mid, int B, float* du, unsigned int seed, unsigned int step,
@@ -782,45 +751,34 @@ static int launch_token_bwd(const m2m_tower* t, int b, const float* g_mid, int B
     if (nw >= 8) return launch_token_bwd_nw<P, DM, TM, 8>(t, b, g_mid, B, du, seed, step, step_dev, st);
     return launch_token_bwd_nw<P, DM, TM, 4>(t, b, g_mid, B, du, seed, step, step_dev, st);
 }
-#define M2M_TOK_DISPATCH_TM(FN, TM_, training_, ...)                                                \
-    do {                                                                                            \
-        const int dm_ = m2m_drop_mode(training_, t->p_drop);                                       \
-        if (t->prec == PREC_BF16) {                                                                 \
-            if (dm_ == DM_NONE) return FN<PREC_BF16, DM_NONE, TM_>(__VA_ARGS__);                   \
-            if (dm_ == DM_HALF) return FN<PREC_BF16, DM_HALF, TM_>(__VA_ARGS__);                   \
-            return FN<PREC_BF16, DM_GEN, TM_>(__VA_ARGS__);                                        \
-        }                                                                                           \
-        if (dm_ == DM_NONE) return FN<PREC_F32, DM_NONE, TM_>(__VA_ARGS__);                        \
-        if (dm_ == DM_HALF) return FN<PREC_F32, DM_HALF, TM_>(__VA_ARGS__);                        \
-        return FN<PREC_F32, DM_GEN, TM_>(__VA_ARGS__);                                             \
-    } while (0)
-#define M2M_TOK_DISPATCH(FN, training_, ...)                                                        \
-    do {                                                                                            \
-        if (t->T <= 16) M2M_TOK_DISPATCH_TM(FN, 16, training_, __VA_ARGS__);                       \
-        M2M_TOK_DISPATCH_TM(FN, 32, training_, __VA_ARGS__);                                       \
-    } while (0)
-
+// f(P, DM) of a token-mixing launch (the precision has passed m2m_check_tower)
+template <class F> static int tok_dispatch(int prec, int training, float p_drop, F&& f) {
+    return m2m_dispatch(m2m_precs{}, prec, M2M_NO_BUILD, [&](auto P) {
+        return m2m_dispatch_dm(training, p_drop, [&](auto DM) { return f(P, DM); });
+    });
+}
+// single-tower launches: hidden units per lane the kernel is built for (TM: 16 for token_dim <= 16, else 32)
 static int token_fwd(const m2m_tower* t, int b, const float* src, long src_ss, int B, float* x_mid, float* save_x_in, int training,
                      unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st) {
-    M2M_TOK_DISPATCH(launch_token_fwd, training, t, b, src, src_ss, B, x_mid, save_x_in, training, seed, step, step_dev, st);
+    return tok_dispatch(t->prec, training, t->p_drop, [&](auto P, auto DM) {
+        if (t->T <= 16) return launch_token_fwd<P(), DM(), 16>(t, b, src, src_ss, B, x_mid, save_x_in, training, seed, step, step_dev, st);
+        return launch_token_fwd<P(), DM(), 32>(t, b, src, src_ss, B, x_mid, save_x_in, training, seed, step, step_dev, st);
+    });
 }
 static int token_bwd(const m2m_tower* t, int b, const float* g_mid, int B, float* du, unsigned int seed, unsigned int step,
                      const unsigned int* step_dev, hipStream_t st) {
-    M2M_TOK_DISPATCH(launch_token_bwd, 1, t, b, g_mid, B, du, seed, step, step_dev, st);
+    return tok_dispatch(t->prec, 1, t->p_drop, [&](auto P, auto DM) {
+        if (t->T <= 16) return launch_token_bwd<P(), DM(), 16>(t, b, g_mid, B, du, seed, step, step_dev, st);
+        return launch_token_bwd<P(), DM(), 32>(t, b, g_mid, B, du, seed, step, step_dev, st);
+    });
 }
 
 // ---- two wide towers per launch (m2m_towers_forward / _backward) ---------------------------------------------------------
 // Conditions (m2m_can_group_wide): same precision, hidden_dim 256, dropout, token_dim class and block count (<= 4), small launches
 // (one column block per workgroup).  MM-IMDb's image and text towers; every launch of the pair is then ONE launch on the main
 // stream: the two-queue form paid two fork / join pairs per step (~5 us per edge in a replayed graph) and staggered launches.
-int m2m_chain_forward_rows_group(const m2m_tower* const* v, const float* const* x0, const long* x0_ss, int B, float* const* out,
-                                 const long* out_ss, int training, unsigned int seed, unsigned int step, const unsigned int* step_dev,
-                                 hipStream_t st);                                                        // tower_fwd.hip
-int m2m_chain_backward_rows_group(const m2m_tower* const* v, int B, const float* const* d_out, const long* d_out_ss,
-                                  const float* const* d_pooled, float* const* d_x0, const long* d_x0_ss, unsigned int seed,
-                                  unsigned int step, const unsigned int* step_dev, hipStream_t st);     // tower_bwd.hip
 bool m2m_can_group_wide(const m2m_tower* a, const m2m_tower* b, int B) {
-    static const int off = [] { const char* e = getenv("M2M_WIDE_GROUP"); return e && e[0] == '0'; }();   // diagnostic (A/B)
+    static const bool off = m2m_env_int("M2M_WIDE_GROUP", 1) == 0;   // diagnostic (A/B)
     if (off || !m2m_is_wide(a) || !m2m_is_wide(b)) return false;
     if (a->prec != b->prec || a->D != b->D || a->D != 256 || a->p_drop != b->p_drop) return false;
     if ((a->T <= 16) != (b->T <= 16) || a->T > 16) return false;        // (16 waves per workgroup: token_dim <= 16)
@@ -835,16 +793,8 @@ static int launch_token_fwd_group(const TokGroupArgs& a, int b, int B, int N, in
     constexpr int NW = 16;
     const TokGeom g = tok_geom(a.tw[0].D);
     const size_t lds = ((tok_lds_floats(N, g.spw, TM) + 3) & ~(size_t)3) * sizeof(float) + (size_t)(NW + 1) * TM * TW_COLS * sizeof(float);
-    auto kern = token_fwd_group_kernel<P, DM, TM, NW>;
-    static size_t attr_lds = 48 * 1024;
-    if (lds > attr_lds) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
     const int mx = a.nblk[0] > a.nblk[1] ? a.nblk[0] : a.nblk[1];
-    hipLaunchKernelGGL(kern, dim3(mx, 2), dim3(NW * 64), lds, st, a, b, B, training, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<token_fwd_group_kernel<P, DM, TM, NW>>(dim3(mx, 2), dim3(NW * 64), lds, tok_fwd_lds_attr(lds), st, a, b, B, training, seed, step, step_dev);
 }
 template <int P, int DM, int TM>
 static int launch_token_bwd_group(const TokGroupArgs& a, int b, int B, int N, int training_unused, unsigned int seed, unsigned int step,
@@ -855,37 +805,21 @@ static int launch_token_bwd_group(const TokGroupArgs& a, int b, int B, int N, in
     const size_t lds = ((tok_lds_floats(N, g.spw, TM) + 3) & ~(size_t)3) * sizeof(float) +
                        ((size_t)2 * TM * TW_LDW + NW * part_f + 2 * N * TM + TM + N) * sizeof(float);
     if (lds > 160 * 1024) { m2m_set_error("token backward (group): tokens x token_dim exceed the workgroup's LDS", __FILE__, __LINE__); return -1; }
-    auto kern = token_bwd_cols_group_kernel<P, DM, TM, NW>;
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
     const int mx = a.nblk[0] > a.nblk[1] ? a.nblk[0] : a.nblk[1];
-    hipLaunchKernelGGL(kern, dim3(mx, 2), dim3(NW * 64), lds, st, a, b, B, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<token_bwd_cols_group_kernel<P, DM, TM, NW>>(dim3(mx, 2), dim3(NW * 64), lds, lds, st, a, b, B, seed, step, step_dev);
 }
 // (both towers: token_dim <= 16 -- m2m_can_group_wide)
-#define M2M_TOKG_DISPATCH(FN, training_, p_drop_, prec_, ...)                                       \
-    do {                                                                                            \
-        const int dm_ = m2m_drop_mode(training_, p_drop_);                                         \
-        if (prec_ == PREC_BF16) {                                                                   \
-            if (dm_ == DM_NONE) return FN<PREC_BF16, DM_NONE, 16>(__VA_ARGS__);                    \
-            if (dm_ == DM_HALF) return FN<PREC_BF16, DM_HALF, 16>(__VA_ARGS__);                    \
-            return FN<PREC_BF16, DM_GEN, 16>(__VA_ARGS__);                                         \
-        }                                                                                           \
-        if (dm_ == DM_NONE) return FN<PREC_F32, DM_NONE, 16>(__VA_ARGS__);                         \
-        if (dm_ == DM_HALF) return FN<PREC_F32, DM_HALF, 16>(__VA_ARGS__);                         \
-        return FN<PREC_F32, DM_GEN, 16>(__VA_ARGS__);                                              \
-    } while (0)
 static int token_fwd_group(const TokGroupArgs& a, int b, int B, int N, int training, unsigned int seed, unsigned int step,
                            const unsigned int* step_dev, hipStream_t st) {
-    M2M_TOKG_DISPATCH(launch_token_fwd_group, training, a.tw[0].p_drop, a.tw[0].prec, a, b, B, N, training, seed, step, step_dev, st);
+    return tok_dispatch(a.tw[0].prec, training, a.tw[0].p_drop, [&](auto P, auto DM) {
+        return launch_token_fwd_group<P(), DM(), 16>(a, b, B, N, training, seed, step, step_dev, st);
+    });
 }
 static int token_bwd_group(const TokGroupArgs& a, int b, int B, int N, unsigned int seed, unsigned int step,
                            const unsigned int* step_dev, hipStream_t st) {
-    M2M_TOKG_DISPATCH(launch_token_bwd_group, 1, a.tw[0].p_drop, a.tw[0].prec, a, b, B, N, 1, seed, step, step_dev, st);
+    return tok_dispatch(a.tw[0].prec, 1, a.tw[0].p_drop, [&](auto P, auto DM) {
+        return launch_token_bwd_group<P(), DM(), 16>(a, b, B, N, 1, seed, step, step_dev, st);
+    });
 }
 
 int m2m_forward_wide_group(const m2m_tower* const* tw, const m2m_tower_io* io, int B, int training, unsigned int seed,
@@ -1029,7 +963,7 @@ int m2m_backward_wide(const m2m_tower* t, int B, const float* d_out, long d_out_
         const long dst_ss = b > 0 ? dense : d_x0_ss;
         // rows per workgroup: 32 (8 per wave) when there are plenty, 8 at small batch so that the chip is not left to 80
         // workgroups, 128 when there are so many that the gamma / beta atomics of thousands of workgroups queue up
-        static const int ln_small = [] { const char* e = getenv("M2M_LN1_SMALL"); return e ? atoi(e) : 1; }();   // diagnostic (A/B)
+        static const int ln_small = m2m_env_int("M2M_LN1_SMALL", 1);   // diagnostic (A/B)
         if (rows < 16384 && ln_small) {                            // 16 waves x 2 rows
             hipLaunchKernelGGL(ln1_bwd_rows_kernel<16>, dim3((unsigned)((rows + LN_ROWS - 1) / LN_ROWS)), dim3(1024), 0, st, bk.x_in, t->ws_b,
                                t->ws_a, bk.ln1_w, rows, t->N, t->D, dst, dst_ss, bk.g_ln1_w, bk.g_ln1_b, LN_ROWS);

@@ -15,8 +15,7 @@
 // tile, Hact^T and dHpre^T (the hidden activation and its gradient leave the chip ONCE, in operand precision, here).
 #include "tile.h"
 #include "token_mfma.h"
-#include "split.h"
-int m2m_split_small_grads(const SplitReduceArgs& a, hipStream_t st);     // split_mix.hip: sum of the per-workgroup slots into the gradients
+#include "dispatch.h"
 #include <algorithm>
 
 // The classification heads + multi-head cross-entropy computed in the PROLOGUE of the fusion tower's backward launch (template
@@ -74,8 +73,7 @@ __device__ int g_bwd_static_split = 1;      // 1: static split of the bf16 colum
 static int bwd_split_mode_init(hipStream_t st) {
     static bool done = false;
     if (done) return 0;
-    const char* e = getenv("M2M_BWD_TICKETS");
-    if (e && atoi(e) != 0) {
+    if (m2m_env_int("M2M_BWD_TICKETS", 0) != 0) {
         const int v = 0;
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         (void)hipStreamIsCapturing(st, &cs);
@@ -1262,7 +1260,7 @@ static_assert(sizeof(BwdGroupArgs) <= 3584, "kernel arguments are limited to 4 K
 // contention) nets -3 us including its reduction launch, and its small gradients no longer depend on the order of the atomics.
 // M2M_SMALL_PART=0 keeps the atomics everywhere.
 static bool m2m_small_part(const m2m_tower* t) {
-    static const int off = [] { const char* e = getenv("M2M_SMALL_PART"); return e && e[0] == '0'; }();
+    static const bool off = m2m_env_int("M2M_SMALL_PART", 1) == 0;
     return !off && t->gpart != nullptr && !m2m_is_wide(t) && t->prec == PREC_BF16 && t->D == 128 && t->nblocks >= 1 &&
            2 * t->T * t->N + t->T + t->N <= SPP_TOK_MAX;
 }
@@ -1284,8 +1282,7 @@ static void m2m_small_part_reduce_args(SplitReduceTower& x, const m2m_tower* t, 
         x.g_b2[L] = k.g_ch_b2;
     }
 }
-bool m2m_split_eligible(const m2m_tower* t, int B, int training);
-// see split.h: the slot reduction of the fused single-tower backward launch (launch_bwd_dm) of tower t at batch B
+// see host.h: the slot reduction of the fused single-tower backward launch (launch_bwd_dm) of tower t at batch B
 bool m2m_small_part_deferred(SplitReduceTower& x, const m2m_tower* t, int B) {
     if (!t || m2m_is_wide(t) || t->N < 1 || t->N > 8 || !m2m_small_part(t) || m2m_split_eligible(t, B, 1)) return false;
     const int SPW = BM / t->N;
@@ -1314,6 +1311,16 @@ template __global__ void tower_bwd_kernel<PREC_BF16, 128, 8, 16, DM_HALF, true, 
 template <int P, int D, int NMAX, int TG>
 static size_t bwd_lds_bytes(int nblocks, int N, int Cp) { return BwdLds<P, D, NMAX, TG>::bytes(nblocks, N, Cp); }
 
+// f(PART, HREC) for the form of the backward kernel: per-workgroup slots for the small gradients (PART), the recompute form of
+// the weight gradients (HREC).  A form whose CAN_ flag is false is not built for the caller's instantiation and never asked for.
+template <bool CAN_PART, bool CAN_HREC, class F>
+static int bwd_forms(bool part, bool hrec, F&& f) {
+    if constexpr (CAN_PART && CAN_HREC) { if (part && hrec) return f(std::true_type{}, std::true_type{}); }
+    if constexpr (CAN_PART) { if (part) return f(std::true_type{}, std::false_type{}); }
+    if constexpr (CAN_HREC) { if (hrec) return f(std::false_type{}, std::true_type{}); }
+    return f(std::false_type{}, std::false_type{});
+}
+
 template <int P, int D, int NMAX, int TG, int DM>
 static int launch_bwd_group_dm(const BwdGroupArgs& a, int B, unsigned int seed, unsigned int step, const unsigned int* step_dev,
                                hipStream_t st, bool hrec_req) {
@@ -1328,31 +1335,17 @@ static int launch_bwd_group_dm(const BwdGroupArgs& a, int B, unsigned int seed, 
     constexpr bool CAN_HREC = P == PREC_BF16 && D == 128 && DM != DM_GEN;   // (m2m_wgrad_recompute's instantiations)
     const bool hrec = CAN_HREC && hrec_req;
     if (hrec_req && !CAN_HREC) { m2m_set_error("towers_backward: recompute form requested for an instantiation without it", __FILE__, __LINE__); return -1; }
-    auto kern = tower_bwd_group_kernel<P, D, NMAX, TG, DM, false, false>;
-    if constexpr (CAN_PART) { if (part) kern = tower_bwd_group_kernel<P, D, NMAX, TG, DM, true, false>; }
-    if constexpr (CAN_HREC) {
-        if (hrec) kern = tower_bwd_group_kernel<P, D, NMAX, TG, DM, false, true>;
-        if constexpr (CAN_PART) { if (hrec && part) kern = tower_bwd_group_kernel<P, D, NMAX, TG, DM, true, true>; }
-    }
-    static bool attr_done[4] = {false, false, false, false};
-    if (!attr_done[part + 2 * hrec]) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, M2M_LDS_MAX));
-        attr_done[part + 2 * hrec] = true;
-    }
     const int mx = a.ntiles[0] > a.ntiles[1] ? a.ntiles[0] : a.ntiles[1];
     const int grid = 8 * ((mx + 3) / 4);                     // see the XCD-aware mapping in the kernel
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHREADS), lds, st, a, B, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return bwd_forms<CAN_PART, CAN_HREC>(part, hrec, [&](auto PART, auto HREC) {
+        return m2m_launch<tower_bwd_group_kernel<P, D, NMAX, TG, DM, PART(), HREC()>>(dim3(grid), dim3(NTHREADS), lds, M2M_LDS_MAX, st, a, B, seed,
+                                                                                     step, step_dev);
+    });
 }
 template <int P, int D, int NMAX, int TG>
 static int launch_bwd_group(const BwdGroupArgs& a, int B, unsigned int seed, unsigned int step, const unsigned int* step_dev,
                             hipStream_t st, bool hrec) {
-    switch (m2m_drop_mode(1, a.tw[0].p_drop)) {
-        case DM_NONE: return launch_bwd_group_dm<P, D, NMAX, TG, DM_NONE>(a, B, seed, step, step_dev, st, hrec);
-        case DM_HALF: return launch_bwd_group_dm<P, D, NMAX, TG, DM_HALF>(a, B, seed, step, step_dev, st, hrec);
-        default:      return launch_bwd_group_dm<P, D, NMAX, TG, DM_GEN>(a, B, seed, step, step_dev, st, hrec);
-    }
+    return m2m_dispatch_dm(1, a.tw[0].p_drop, [&](auto DM) { return launch_bwd_group_dm<P, D, NMAX, TG, DM()>(a, B, seed, step, step_dev, st, hrec); });
 }
 
 template <int P, int D, int NMAX, int TG, int DM>
@@ -1366,19 +1359,11 @@ static int launch_bwd_dm(const m2m_tower* t, int B, const float* d_out, long d_o
     const bool part = CAN_PART && m2m_small_part(t);
     constexpr bool CAN_HREC = P == PREC_BF16 && D == 128 && DM != DM_GEN;
     const bool hrec = CAN_HREC && m2m_wgrad_recompute(t, B);
-    auto kern = tower_bwd_kernel<P, D, NMAX, TG, DM, false, false>;
-    if constexpr (CAN_PART) { if (part) kern = tower_bwd_kernel<P, D, NMAX, TG, DM, true, false>; }
-    if constexpr (CAN_HREC) {
-        if (hrec) kern = tower_bwd_kernel<P, D, NMAX, TG, DM, false, true>;
-        if constexpr (CAN_PART) { if (hrec && part) kern = tower_bwd_kernel<P, D, NMAX, TG, DM, true, true>; }
-    }
-    static bool attr_done[4] = {false, false, false, false};
-    if (!attr_done[part + 2 * hrec]) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, M2M_LDS_MAX));
-        attr_done[part + 2 * hrec] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHREADS), lds, st, *t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
+    const int rc = bwd_forms<CAN_PART, CAN_HREC>(part, hrec, [&](auto PART, auto HREC) {
+        return m2m_launch<tower_bwd_kernel<P, D, NMAX, TG, DM, PART(), HREC()>>(dim3(grid), dim3(NTHREADS), lds, M2M_LDS_MAX, st, *t, B, d_out, d_out_ss,
+                                                                               d_pooled, d_x0, d_x0_ss, seed, step, step_dev);
+    });
+    if (rc) return rc;
     if (part && !(t->wgrad_flags & M2M_WGRAD_REDUCES_SMALL)) {       // (flagged: the next weight-gradient launch reduces the slots)
         SplitReduceArgs r;
         memset(&r, 0, sizeof(r));
@@ -1398,15 +1383,11 @@ static int launch_bwd_heads_dm(const m2m_tower* t, int B, const BwdHeads& hd, fl
     if (lds > M2M_LDS_MAX || t->Cp > 8 * NTHREADS) { m2m_set_error("tower_backward_heads: blocks x channel_dim exceed the workgroup's LDS", __FILE__, __LINE__); return -1; }
     constexpr bool CAN_HREC = DM != DM_GEN;
     const bool hrec = CAN_HREC && m2m_wgrad_recompute(t, B);
-    auto kern = tower_bwd_heads_kernel<P, D, NMAX, TG, DM, false>;
-    if constexpr (CAN_HREC) { if (hrec) kern = tower_bwd_heads_kernel<P, D, NMAX, TG, DM, true>; }
-    static bool attr_done[2] = {false, false};
-    if (!attr_done[hrec]) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, M2M_LDS_MAX));
-        attr_done[hrec] = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHREADS), lds, st, *t, hd, B, d_x0, d_x0_ss, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
+    const int rc = bwd_forms<false, CAN_HREC>(false, hrec, [&](auto, auto HREC) {
+        return m2m_launch<tower_bwd_heads_kernel<P, D, NMAX, TG, DM, HREC()>>(dim3(grid), dim3(NTHREADS), lds, M2M_LDS_MAX, st, *t, hd, B, d_x0, d_x0_ss,
+                                                                             seed, step, step_dev);
+    });
+    if (rc) return rc;
     SplitReduceArgs r;
     memset(&r, 0, sizeof(r));
     r.ntow = 1;
@@ -1417,38 +1398,24 @@ static int launch_bwd_heads_dm(const m2m_tower* t, int B, const BwdHeads& hd, fl
 template <int P, int D, int NMAX, int TG>
 static int launch_bwd(const m2m_tower* t, int B, const float* d_out, long d_out_ss, const float* d_pooled, float* d_x0,
                       long d_x0_ss, unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st) {
-    switch (m2m_drop_mode(1, t->p_drop)) {
-        case DM_NONE: return launch_bwd_dm<P, D, NMAX, TG, DM_NONE>(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);
-        case DM_HALF: return launch_bwd_dm<P, D, NMAX, TG, DM_HALF>(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);
-        default:      return launch_bwd_dm<P, D, NMAX, TG, DM_GEN>(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);
-    }
+    return m2m_dispatch_dm(1, t->p_drop, [&](auto DM) {
+        return launch_bwd_dm<P, D, NMAX, TG, DM()>(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);
+    });
 }
 
-int m2m_check_tower(const m2m_tower* t, int B);
-bool m2m_wgrad_recompute(const m2m_tower* t, int B);     // tower_wgrad.hip
-int m2m_backward_wide(const m2m_tower* t, int B, const float* d_out, long d_out_ss, const float* d_pooled, float* d_x0,
-                      long d_x0_ss, unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st);
-
-// Backward of the channel-mixing half of ONE block (+ final LayerNorm if the view has it) over B*N independent rows.
+// (host.h) the wide path's per-block launch: NMAX = 0, channel mixing only
 int m2m_chain_backward_rows(const m2m_tower* t, int B, const float* d_out, long d_out_ss, const float* d_pooled, float* d_x0,
                             long d_x0_ss, unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st) {
     if (int rc = bwd_split_mode_init(st)) return rc;
-#define M2M_BWDR_CASE(PP, DD) \
-    if (t->prec == PP && t->D == DD) return launch_bwd<PP, DD, 0, 8>(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);
-    M2M_BWDR_CASE(PREC_BF16, 32) M2M_BWDR_CASE(PREC_BF16, 64) M2M_BWDR_CASE(PREC_BF16, 128) M2M_BWDR_CASE(PREC_BF16, 256)
-    M2M_BWDR_CASE(PREC_F32, 32) M2M_BWDR_CASE(PREC_F32, 64) M2M_BWDR_CASE(PREC_F32, 128) M2M_BWDR_CASE(PREC_F32, 256)
-#undef M2M_BWDR_CASE
+    const int rc = m2m_dispatch_pd(m2m_wide_dims{}, t->prec, t->D, [&](auto P, auto D) {
+        return launch_bwd<P(), D(), 0, 8>(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);
+    });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("tower_backward (wide): unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }
 
-bool m2m_can_group(const m2m_tower* a, const m2m_tower* b);
-bool m2m_split_eligible(const m2m_tower* t, int B, int training);
-bool m2m_split_can_group(const m2m_tower* a, const m2m_tower* b);
-int m2m_split_backward(const m2m_tower* const* towers, const m2m_tower_gio* io, int ntow, int B, unsigned int seed, unsigned int step,
-                       const unsigned int* step_dev, hipStream_t st);
-
-// Channel-mixing halves (wide path) of two towers' blocks in one launch (token_wide.hip: m2m_backward_wide_group).
+// (host.h) v[i] = block views (token_wide.hip: m2m_backward_wide_group)
 int m2m_chain_backward_rows_group(const m2m_tower* const* v, int B, const float* const* d_out, const long* d_out_ss,
                                   const float* const* d_pooled, float* const* d_x0, const long* d_x0_ss, unsigned int seed,
                                   unsigned int step, const unsigned int* step_dev, hipStream_t st) {
@@ -1462,14 +1429,13 @@ int m2m_chain_backward_rows_group(const m2m_tower* const* v, int B, const float*
         a.ntiles[i] = (int)(((long)B * v[i]->N + BM - 1) / BM);
     }
     const m2m_tower* t = v[0];
-    if (t->D == 256 && t->prec == PREC_BF16) return launch_bwd_group<PREC_BF16, 256, 0, 8>(a, B, seed, step, step_dev, st, false);
-    if (t->D == 256 && t->prec == PREC_F32) return launch_bwd_group<PREC_F32, 256, 0, 8>(a, B, seed, step, step_dev, st, false);
+    const int rc = m2m_dispatch_pd(m2m_pair_dims{}, t->prec, t->D, [&](auto P, auto D) {
+        return launch_bwd_group<P(), D(), 0, 8>(a, B, seed, step, step_dev, st, false);
+    });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("towers_backward (wide): hidden_dim 256 only", __FILE__, __LINE__);
     return -1;
 }
-bool m2m_can_group_wide(const m2m_tower* a, const m2m_tower* b, int B);       // token_wide.hip
-int m2m_backward_wide_group(const m2m_tower* const* tw, const m2m_tower_gio* io, int B, unsigned int seed, unsigned int step,
-                            const unsigned int* step_dev, hipStream_t st);
 
 extern "C" int m2m_towers_backward(const m2m_tower* const* towers, const m2m_tower_gio* io, int ntowers, int B, uint32_t seed,
                                    uint32_t step, const uint32_t* step_dev, void* stream) {
@@ -1507,7 +1473,7 @@ extern "C" int m2m_towers_backward(const m2m_tower* const* towers, const m2m_tow
     // (two-tower launch: measured a net LOSS -- the slot form of this instantiation spills 7 registers around the column loop
     // and its reduction launch costs what the 128-way contended atomics cost -- so it stays opt-in: M2M_SMALL_PART=2)
     // With M2M_WGRAD_GROUP_SLOTS + M2M_WGRAD_REDUCES_SMALL on both towers the reduction rides in the weight-gradient launch.
-    static const bool group_part = [] { const char* e = getenv("M2M_SMALL_PART"); return e && e[0] == '2'; }();
+    static const bool group_part = m2m_env_int("M2M_SMALL_PART", 1) == 2;
     const bool flagged = (towers[0]->wgrad_flags & M2M_WGRAD_GROUP_SLOTS) && (towers[1]->wgrad_flags & M2M_WGRAD_GROUP_SLOTS);
     const bool part = (group_part || flagged) && m2m_small_part(towers[0]) && m2m_small_part(towers[1]);
     const bool defer = flagged && (towers[0]->wgrad_flags & M2M_WGRAD_REDUCES_SMALL) && (towers[1]->wgrad_flags & M2M_WGRAD_REDUCES_SMALL);
@@ -1537,15 +1503,12 @@ extern "C" int m2m_towers_backward(const m2m_tower* const* towers, const m2m_tow
         for (int i = 0; i < 2; ++i) m2m_small_part_reduce_args(r.t[i], towers[i], a.ntiles[i]);
         return m2m_split_small_grads(r, st);
     };
-#define M2M_BWDG_CASE(PP, DD) \
-    if (t->prec == PP && t->D == DD) {                                                                          \
-        if (t->N <= 4) return finish(launch_bwd_group<PP, DD, 4, 8>(a, B, seed, step, step_dev, st, hrec));           \
-        if (t->T % 16 == 0) return finish(launch_bwd_group<PP, DD, 8, 16>(a, B, seed, step, step_dev, st, hrec));     \
-        return finish(launch_bwd_group<PP, DD, 8, 8>(a, B, seed, step, step_dev, st, hrec));                          \
-    }
-    M2M_BWDG_CASE(PREC_BF16, 32) M2M_BWDG_CASE(PREC_BF16, 64) M2M_BWDG_CASE(PREC_BF16, 128)
-    M2M_BWDG_CASE(PREC_F32, 32) M2M_BWDG_CASE(PREC_F32, 64) M2M_BWDG_CASE(PREC_F32, 128)
-#undef M2M_BWDG_CASE
+    const int rc = m2m_dispatch_pd(m2m_fused_dims{}, t->prec, t->D, [&](auto P, auto D) {
+        return m2m_fused_class(t->N, t->T, [&](auto NMAX, auto TG) {
+            return finish(launch_bwd_group<P(), D(), NMAX(), TG()>(a, B, seed, step, step_dev, st, hrec));
+        });
+    });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("towers_backward: unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }
@@ -1558,7 +1521,7 @@ extern "C" int m2m_tower_backward_heads_ok(const m2m_tower* t, int B, int nheads
     // process: fusion backward + heads in one launch 80.3-80.9 us against 68.2-69.3 + 13.6-14.1 us as two launches -- the heads'
     // latency chain (token means and head weights from L2 -> logits -> softmax -> gradients -> 15 KB of slot stores per
     // workgroup) costs ~12 us in front of the backward's own prologue, what the separate launch cost; step time unchanged.
-    static const int on = [] { const char* e = getenv("M2M_FUSED_HEADS"); return e && e[0] == '1'; }();
+    static const bool on = m2m_env_int("M2M_FUSED_HEADS", 0) == 1;
     if (!on || !m2m_small_part(t) || m2m_split_eligible(t, B, 1)) return 0;
     if (nheads < 1 || nheads > BH_MAXH || K < 2 || K * t->D + K + 2 > SPP_STRIDE || K > 16) return 0;
     return 1;
@@ -1580,15 +1543,12 @@ extern "C" int m2m_tower_backward_heads(const m2m_tower* t, int B, const m2m_hea
     }
     hd.labels = labels; hd.logits = logits; hd.preds = preds; hd.nheads = nheads; hd.K = K; hd.own = own;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const int dm = m2m_drop_mode(1, t->p_drop);
-#define M2M_BWDH_CASE(NM, TGG) \
-    { if (dm == DM_NONE) return launch_bwd_heads_dm<PREC_BF16, 128, NM, TGG, DM_NONE>(t, B, hd, losses, d_x0, d_x0_ss, seed, step, step_dev, st); \
-      if (dm == DM_HALF) return launch_bwd_heads_dm<PREC_BF16, 128, NM, TGG, DM_HALF>(t, B, hd, losses, d_x0, d_x0_ss, seed, step, step_dev, st); \
-      return launch_bwd_heads_dm<PREC_BF16, 128, NM, TGG, DM_GEN>(t, B, hd, losses, d_x0, d_x0_ss, seed, step, step_dev, st); }
-    if (t->N <= 4) M2M_BWDH_CASE(4, 8)
-    if (t->T % 16 == 0) M2M_BWDH_CASE(8, 16)
-    M2M_BWDH_CASE(8, 8)
-#undef M2M_BWDH_CASE
+    // bf16, hidden_dim 128 only (m2m_small_part)
+    return m2m_fused_class(t->N, t->T, [&](auto NMAX, auto TG) {
+        return m2m_dispatch_dm(1, t->p_drop, [&](auto DM) {
+            return launch_bwd_heads_dm<PREC_BF16, 128, NMAX(), TG(), DM()>(t, B, hd, losses, d_x0, d_x0_ss, seed, step, step_dev, st);
+        });
+    });
 }
 
 extern "C" int m2m_tower_backward(const m2m_tower* t, int B, const float* d_out, int64_t d_out_ss, const float* d_pooled,
@@ -1602,15 +1562,12 @@ extern "C" int m2m_tower_backward(const m2m_tower* t, int B, const float* d_out,
         io1.d_out = d_out; io1.d_out_sample_stride = d_out_ss; io1.d_pooled = d_pooled; io1.d_x0 = d_x0; io1.d_x0_sample_stride = d_x0_ss;
         return m2m_split_backward(&t, &io1, 1, B, seed, step, step_dev, st);
     }
-#define M2M_BWD_CASE(PP, DD) \
-    if (t->prec == PP && t->D == DD) {                                                                                          \
-        if (t->N <= 4) return launch_bwd<PP, DD, 4, 8>(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);   \
-        if (t->T % 16 == 0) return launch_bwd<PP, DD, 8, 16>(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st); \
-        return launch_bwd<PP, DD, 8, 8>(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);                \
-    }
-    M2M_BWD_CASE(PREC_BF16, 32) M2M_BWD_CASE(PREC_BF16, 64) M2M_BWD_CASE(PREC_BF16, 128)
-    M2M_BWD_CASE(PREC_F32, 32) M2M_BWD_CASE(PREC_F32, 64) M2M_BWD_CASE(PREC_F32, 128)
-#undef M2M_BWD_CASE
+    const int rc = m2m_dispatch_pd(m2m_fused_dims{}, t->prec, t->D, [&](auto P, auto D) {
+        return m2m_fused_class(t->N, t->T, [&](auto NMAX, auto TG) {
+            return launch_bwd<P(), D(), NMAX(), TG()>(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);
+        });
+    });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("tower_backward: unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }

@@ -15,6 +15,7 @@
 #include "tile.h"
 #include "token_mfma.h"
 #include "embed_fwd.h"
+#include "dispatch.h"
 #include <algorithm>
 
 // LDS budget of the forward chain kernel (bytes): FIXED + nblocks * PB * 4
@@ -550,44 +551,25 @@ static int launch_fwd_dm(const m2m_tower* t, const float* x0, long x0_ss, int B,
     const int grid = NMAX > 0 ? (B + SPW - 1) / SPW : (int)(((long)B * t->N + BM - 1) / BM);
     const size_t lds = fwd_lds_bytes<P, D, NMAX>(t->nblocks, t->N, t->Cp);
     if (lds > M2M_LDS_MAX || t->Cp > 8 * NTHREADS) { m2m_set_error("tower_forward: blocks x channel_dim exceed the workgroup's LDS", __FILE__, __LINE__); return -1; }
-    auto kern = tower_fwd_kernel<P, D, NMAX, DM>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, M2M_LDS_MAX));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHREADS), lds, st, *t, x0, x0_ss, B, out, out_ss, pooled, training, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<tower_fwd_kernel<P, D, NMAX, DM>>(dim3(grid), dim3(NTHREADS), lds, M2M_LDS_MAX, st, *t, x0, x0_ss, B, out, out_ss, pooled,
+                                                        training, seed, step, step_dev);
 }
 
 template <int P, int D, int NMAX>
 static int launch_fwd(const m2m_tower* t, const float* x0, long x0_ss, int B, float* out, long out_ss, float* pooled,
                       int training, unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st) {
-    switch (m2m_drop_mode(training, t->p_drop)) {
-        case DM_NONE: return launch_fwd_dm<P, D, NMAX, DM_NONE>(t, x0, x0_ss, B, out, out_ss, pooled, training, seed, step, step_dev, st);
-        case DM_HALF: return launch_fwd_dm<P, D, NMAX, DM_HALF>(t, x0, x0_ss, B, out, out_ss, pooled, training, seed, step, step_dev, st);
-        default:      return launch_fwd_dm<P, D, NMAX, DM_GEN>(t, x0, x0_ss, B, out, out_ss, pooled, training, seed, step, step_dev, st);
-    }
+    return m2m_dispatch_dm(training, t->p_drop, [&](auto DM) {
+        return launch_fwd_dm<P, D, NMAX, DM()>(t, x0, x0_ss, B, out, out_ss, pooled, training, seed, step, step_dev, st);
+    });
 }
 
-int m2m_check_tower(const m2m_tower* t, int B);
-bool m2m_split_eligible(const m2m_tower* t, int B, int training);
-bool m2m_split_can_group(const m2m_tower* a, const m2m_tower* b);
-int m2m_split_forward(const m2m_tower* const* towers, const m2m_tower_io* io, int ntow, int B, int training, unsigned int seed,
-                      unsigned int step, const unsigned int* step_dev, hipStream_t st);
-int m2m_forward_wide(const m2m_tower* t, const float* x0, long x0_ss, int B, float* out, long out_ss, float* pooled,
-                     int training, unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st);
-
-// Channel-mixing half of ONE block (+ final LayerNorm if the view has it) over B*N independent rows: the wide path's
-// per-block launch.  `view` is a one-block copy of the tower (token parameters unused).
+// (host.h) the wide path's per-block launch: NMAX = 0, channel mixing only
 int m2m_chain_forward_rows(const m2m_tower* t, const float* x0, long x0_ss, int B, float* out, long out_ss, int training,
                            unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st) {
-#define M2M_FWDR_CASE(PP, DD) \
-    if (t->prec == PP && t->D == DD) return launch_fwd<PP, DD, 0>(t, x0, x0_ss, B, out, out_ss, nullptr, training, seed, step, step_dev, st);
-    M2M_FWDR_CASE(PREC_BF16, 32) M2M_FWDR_CASE(PREC_BF16, 64) M2M_FWDR_CASE(PREC_BF16, 128) M2M_FWDR_CASE(PREC_BF16, 256)
-    M2M_FWDR_CASE(PREC_F32, 32) M2M_FWDR_CASE(PREC_F32, 64) M2M_FWDR_CASE(PREC_F32, 128) M2M_FWDR_CASE(PREC_F32, 256)
-#undef M2M_FWDR_CASE
+    const int rc = m2m_dispatch_pd(m2m_wide_dims{}, t->prec, t->D, [&](auto P, auto D) {
+        return launch_fwd<P(), D(), 0>(t, x0, x0_ss, B, out, out_ss, nullptr, training, seed, step, step_dev, st);
+    });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("tower_forward (wide): unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }
@@ -601,29 +583,19 @@ static int launch_fwd_group_dm(const FwdGroupArgs& a, int B, int training, unsig
         m2m_set_error("towers_forward: blocks x channel_dim exceed the workgroup's LDS", __FILE__, __LINE__);
         return -1;
     }
-    auto kern = tower_fwd_group_kernel<P, D, NMAX, DM>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, M2M_LDS_MAX));
-        attr_done = true;
-    }
     const int mx = a.ntiles[0] > a.ntiles[1] ? a.ntiles[0] : a.ntiles[1];
     const int grid = 8 * ((mx + 3) / 4);                     // see the XCD-aware mapping in the kernel
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NTHREADS), lds, st, a, B, training, seed, step, step_dev);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<tower_fwd_group_kernel<P, D, NMAX, DM>>(dim3(grid), dim3(NTHREADS), lds, M2M_LDS_MAX, st, a, B, training, seed, step, step_dev);
 }
 template <int P, int D, int NMAX>
 static int launch_fwd_group(const FwdGroupArgs& a, int B, int training, unsigned int seed, unsigned int step,
                             const unsigned int* step_dev, hipStream_t st) {
-    switch (m2m_drop_mode(training, a.tw[0].p_drop)) {
-        case DM_NONE: return launch_fwd_group_dm<P, D, NMAX, DM_NONE>(a, B, training, seed, step, step_dev, st);
-        case DM_HALF: return launch_fwd_group_dm<P, D, NMAX, DM_HALF>(a, B, training, seed, step, step_dev, st);
-        default:      return launch_fwd_group_dm<P, D, NMAX, DM_GEN>(a, B, training, seed, step, step_dev, st);
-    }
+    return m2m_dispatch_dm(training, a.tw[0].p_drop, [&](auto DM) {
+        return launch_fwd_group_dm<P, D, NMAX, DM()>(a, B, training, seed, step, step_dev, st);
+    });
 }
 
-// Channel-mixing halves (wide path) of two towers' blocks in one launch: v[i] = block views (token_wide.hip: m2m_forward_wide_group).
+// (host.h) v[i] = block views (token_wide.hip: m2m_forward_wide_group)
 int m2m_chain_forward_rows_group(const m2m_tower* const* v, const float* const* x0, const long* x0_ss, int B, float* const* out,
                                  const long* out_ss, int training, unsigned int seed, unsigned int step, const unsigned int* step_dev,
                                  hipStream_t st) {
@@ -636,16 +608,14 @@ int m2m_chain_forward_rows_group(const m2m_tower* const* v, const float* const* 
         a.ntiles[i] = (int)(((long)B * v[i]->N + BM - 1) / BM);
     }
     const m2m_tower* t = v[0];
-    if (t->D == 256 && t->prec == PREC_BF16) return launch_fwd_group<PREC_BF16, 256, 0>(a, B, training, seed, step, step_dev, st);
-    if (t->D == 256 && t->prec == PREC_F32) return launch_fwd_group<PREC_F32, 256, 0>(a, B, training, seed, step, step_dev, st);
+    const int rc = m2m_dispatch_pd(m2m_pair_dims{}, t->prec, t->D, [&](auto P, auto D) {
+        return launch_fwd_group<P(), D(), 0>(a, B, training, seed, step, step_dev, st);
+    });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("towers_forward (wide): hidden_dim 256 only", __FILE__, __LINE__);
     return -1;
 }
-bool m2m_can_group_wide(const m2m_tower* a, const m2m_tower* b, int B);       // token_wide.hip
-int m2m_forward_wide_group(const m2m_tower* const* tw, const m2m_tower_io* io, int B, int training, unsigned int seed,
-                           unsigned int step, const unsigned int* step_dev, hipStream_t st);
 
-// True when two towers can share one chain launch: both on the fused path, same kernel instantiation, <= 4 blocks each.
 bool m2m_can_group(const m2m_tower* a, const m2m_tower* b) {
     if (m2m_is_wide(a) || m2m_is_wide(b)) return false;
     if (a->prec != b->prec || a->D != b->D || a->p_drop != b->p_drop) return false;
@@ -658,7 +628,6 @@ extern "C" int m2m_towers_can_group(const m2m_tower* a, const m2m_tower* b, int 
     return (m2m_can_group(a, b) || m2m_can_group_wide(a, b, B)) ? 1 : 0;
 }
 
-int m2m_check_embed(const m2m_embed* e, int B);          // embed.hip
 // 1: m2m_towers_forward_embeds takes these towers / embeddings at batch B (fused-path pair, whole samples per 16-row tile,
 // embedding and tower of one hidden_dim / precision); 0: run m2m_embeds_forward + m2m_towers_forward
 extern "C" int m2m_towers_forward_embeds_ok(const m2m_tower* const* towers, int ntowers, const m2m_embed* const* embeds, int B) {
@@ -737,12 +706,12 @@ static int towers_forward_impl(const m2m_tower* const* towers, const m2m_tower_i
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const m2m_tower* t = towers[0];
-#define M2M_FWDG_CASE(PP, DD) \
-    if (t->prec == PP && t->D == DD) return t->N <= 4 ? launch_fwd_group<PP, DD, 4>(a, B, training, seed, step, step_dev, st) \
-                                                      : launch_fwd_group<PP, DD, 8>(a, B, training, seed, step, step_dev, st);
-    M2M_FWDG_CASE(PREC_BF16, 32) M2M_FWDG_CASE(PREC_BF16, 64) M2M_FWDG_CASE(PREC_BF16, 128)
-    M2M_FWDG_CASE(PREC_F32, 32) M2M_FWDG_CASE(PREC_F32, 64) M2M_FWDG_CASE(PREC_F32, 128)
-#undef M2M_FWDG_CASE
+    const int rc = m2m_dispatch_pd(m2m_fused_dims{}, t->prec, t->D, [&](auto P, auto D) {
+        return m2m_fused_class(t->N, t->T, [&](auto NMAX, auto) {
+            return launch_fwd_group<P(), D(), NMAX()>(a, B, training, seed, step, step_dev, st);
+        });
+    });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("towers_forward: unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }
@@ -758,12 +727,12 @@ extern "C" int m2m_tower_forward(const m2m_tower* t, const float* x0, int64_t x0
         io1.x0_parts = 1; io1.x0_part_stride = 0;
         return m2m_split_forward(&t, &io1, 1, B, training, seed, step, step_dev, st);
     }
-#define M2M_FWD_CASE(PP, DD) \
-    if (t->prec == PP && t->D == DD) return t->N <= 4 ? launch_fwd<PP, DD, 4>(t, x0, x0_ss, B, out, out_ss, pooled, training, seed, step, step_dev, st) \
-                                                      : launch_fwd<PP, DD, 8>(t, x0, x0_ss, B, out, out_ss, pooled, training, seed, step, step_dev, st);
-    M2M_FWD_CASE(PREC_BF16, 32) M2M_FWD_CASE(PREC_BF16, 64) M2M_FWD_CASE(PREC_BF16, 128)
-    M2M_FWD_CASE(PREC_F32, 32) M2M_FWD_CASE(PREC_F32, 64) M2M_FWD_CASE(PREC_F32, 128)
-#undef M2M_FWD_CASE
+    const int rc = m2m_dispatch_pd(m2m_fused_dims{}, t->prec, t->D, [&](auto P, auto D) {
+        return m2m_fused_class(t->N, t->T, [&](auto NMAX, auto) {
+            return launch_fwd<P(), D(), NMAX()>(t, x0, x0_ss, B, out, out_ss, pooled, training, seed, step, step_dev, st);
+        });
+    });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("tower_forward: unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }

@@ -15,10 +15,8 @@
 // zeroed gradient with float atomics (a + b == b + a: still bit-deterministic).
 #include "tile.h"
 #include "embed_wgrad.h"
-#include "split.h"
-#include <stdlib.h>
+#include "dispatch.h"
 #include <string.h>
-bool m2m_split_eligible(const m2m_tower* t, int B, int training);     // split_api.hip
 
 // address-space qualifier for pointers known to be global memory (device pass only; the host pass just parses)
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -546,10 +544,6 @@ __global__ __launch_bounds__(256, 2) void embed_wgrad_fast_group_kernel(const Em
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------
-static int wgrad_env(const char* name, int dflt) {
-    const char* e = getenv(name);
-    return e ? atoi(e) : dflt;
-}
 // The recompute form: bf16, hidden_dim 128, dropout off or p == 0.5 (the one-bit keep stream), and not a tower the split path
 // takes (its chain launches store both hidden operands).  OFF by default (M2M_WGRAD_RECOMP=1 enables it): measured on
 // M2-Mixer-B, batch 512, the merged launch takes 134-142 us against 111-115 us for the stored-operand form -- the launch
@@ -558,7 +552,7 @@ static int wgrad_env(const char* name, int dflt) {
 // SIMDs hold ONE wave, so nothing overlaps that issue stream (in-kernel timers, scripts/rc_timers.py: 1.05 us of compute,
 // 0.29 us of DMA issue, 0.25 us of DMA wait per 32-row step).  DESIGN.md section 4e.
 bool m2m_wgrad_recompute(const m2m_tower* t, int B) {
-    static const int on = wgrad_env("M2M_WGRAD_RECOMP", 0);
+    static const int on = m2m_env_int("M2M_WGRAD_RECOMP", 0);
     if (!on || t->prec != PREC_BF16 || t->D != 128 || t->nblocks < 1 || t->Cp < 64) return false;
     if (m2m_drop_mode(1, t->p_drop) == DM_GEN) return false;
     if (m2m_split_eligible(t, B, 1)) return false;
@@ -569,7 +563,7 @@ extern "C" int m2m_wgrad_form(const m2m_tower* t, int B) { return t && m2m_wgrad
 // The partial-gradient slot can stand in for a second row group when the three channel-mixing gradients of every block lie
 // back to back ([dW1 | db1 | dW2], the flat engines' layout), because the slot is folded in as ONE range per block.
 static bool wgrad_slot_usable(const m2m_tower* t) {
-    static const int on = wgrad_env("M2M_WGRAD_SLOT", 1);
+    static const int on = m2m_env_int("M2M_WGRAD_SLOT", 1);
     if (!on || t->nblocks < 1) return false;
     for (int b = 0; b < t->nblocks; ++b) {
         const m2m_block& k = t->blk[b];
@@ -580,7 +574,7 @@ static bool wgrad_slot_usable(const m2m_tower* t) {
 }
 
 // M2M_WGRAD_DMA=0: the register-staged stored-operand loop (A/B)
-static int wgrad_use_dma() { static const int on = wgrad_env("M2M_WGRAD_DMA", 1); return on; }
+static int wgrad_use_dma() { static const int on = m2m_env_int("M2M_WGRAD_DMA", 1); return on; }
 
 struct WgradPlan { int ntiles, nsl, groups, tpg, rpt, slot; };
 // honour_overwrite == false: the plan the tower would get if its gradient were zeroed and accumulated (m2m_wgrad_groups)
@@ -599,8 +593,8 @@ static WgradPlan wgrad_plan(const m2m_tower* t, int B, int cols, bool honour_ove
     const int wgs = nsl * t->nblocks;
     while (wgs * groups < 128 && (ntiles + groups - 1) / groups > 64) ++groups;
     if (groups < (32 + wgs - 1) / wgs) groups = (32 + wgs - 1) / wgs;
-    if (const char* e = getenv("M2M_WGRAD_GROUPS")) groups = atoi(e);   // diagnostic override (scripts/wgrad_probe.py sweeps it); unset in production
-    if (const char* e = getenv("M2M_WGRAD_LONG_GROUPS")) { if (ntiles > 64) groups = atoi(e); }   // diagnostic: towers with more than 64 steps only
+    groups = m2m_env_int("M2M_WGRAD_GROUPS", groups);   // diagnostic override, read per call (scripts/wgrad_probe.py sweeps it); unset in production
+    if (ntiles > 64) groups = m2m_env_int("M2M_WGRAD_LONG_GROUPS", groups);   // diagnostic: towers with more than 64 steps only
     if (honour_overwrite && (t->wgrad_flags & M2M_WGRAD_OVERWRITE)) groups = 1;
     if (groups < 1) groups = 1;
     int tpg = (ntiles + groups - 1) / groups;
@@ -627,16 +621,8 @@ static int launch_wgrad(const m2m_tower* t, int B, unsigned int seed, unsigned i
     typedef WgradKernelGeom<P, D, RCDM> KG;
     const WgradPlan pl = wgrad_plan(t, B, KG::COLS);
     const size_t lds = (size_t)KG::LDS_B;
-    auto kern = tower_wgrad_kernel<P, D, RCDM>;
-    static bool attr_done = false;
-    if (!attr_done) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(pl.nsl, t->nblocks, pl.groups), dim3(KG::THREADS), lds, st, *t, pl.ntiles, pl.tpg, 0, pl.rpt, seed, step,
-                       step_dev, wgrad_use_dma());
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<tower_wgrad_kernel<P, D, RCDM>>(dim3(pl.nsl, t->nblocks, pl.groups), dim3(KG::THREADS), lds, lds, st, *t, pl.ntiles, pl.tpg, 0,
+                                                      pl.rpt, seed, step, step_dev, wgrad_use_dma());
 }
 
 // Plans of a multi-tower launch: per tower as above; then, for a tower with a usable partial-gradient slot (m2m_tower.wslot),
@@ -715,7 +701,7 @@ static int launch_wgrad_group(const m2m_tower* const* host, const m2m_tower* con
     if (nembeds) {
         n_embed_wgs = (P == PREC_BF16 && nembeds == EMB_GROUP) ? embed_wgrad_group_args_fast(ea, embeds, inputs, embed_towers, B) : 0;
         if (n_embed_wgs) lds_e = embed_wgrad_fast_lds<D, KG::THREADS>();
-        else if (KG::THREADS == 256) { static const int ewgs = wgrad_env("M2M_EMBED_WGS", D >= 256 ? 128 : 512);   /* every row group adds 64 x D floats with atomics: at D = 256 (MM-IMDb, batch 32) 512 workgroups were 34 MB of them */ n_embed_wgs = embed_wgrad_group_args(ea, embeds, inputs, d_x0s, B, ewgs, nembeds); lds_e = embed_wgrad_lds<D, P>(); }
+        else if (KG::THREADS == 256) { static const int ewgs = m2m_env_int("M2M_EMBED_WGS", D >= 256 ? 128 : 512);   /* every row group adds 64 x D floats with atomics: at D = 256 (MM-IMDb, batch 32) 512 workgroups were 34 MB of them */ n_embed_wgs = embed_wgrad_group_args(ea, embeds, inputs, d_x0s, B, ewgs, nembeds); lds_e = embed_wgrad_lds<D, P>(); }
         else embeds_separately = true;
     }
     if (embeds_separately) {
@@ -723,29 +709,19 @@ static int launch_wgrad_group(const m2m_tower* const* host, const m2m_tower* con
         else if (int rc = m2m_embeds_wgrad(embeds, inputs, d_x0s, nembeds, B, (void*)st)) return rc;
     }
     if constexpr (P == PREC_BF16) {
-        static const int merged = wgrad_env("M2M_EMBED_MERGED", 1);
+        static const int merged = m2m_env_int("M2M_EMBED_MERGED", 1);
         if (n_embed_wgs && ea.fast && !merged && KG::THREADS != 256) {
             const size_t le = embed_wgrad_fast_lds<D, 256>();
-            auto ek = embed_wgrad_fast_group_kernel<D>;
-            static bool eattr = false;
-            if (!eattr) { M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(ek), hipFuncAttributeMaxDynamicSharedMemorySize, (int)le)); eattr = true; }
-            hipLaunchKernelGGL(ek, dim3((unsigned)n_embed_wgs), dim3(256), le, st, ea);
-            M2M_CHECK_HIP(hipGetLastError());
+            if (int rc = m2m_launch<embed_wgrad_fast_group_kernel<D>>(dim3((unsigned)n_embed_wgs), dim3(256), le, le, st, ea)) return rc;
             n_embed_wgs = 0; lds_e = 0;
         }
     }
     const size_t lds_t = (size_t)KG::LDS_B;
     const size_t lds = lds_t > lds_e ? lds_t : lds_e;
-    auto kern = tower_wgrad_group_kernel<P, D, RCDM>;
-    static size_t attr_lds = 0;
-    if (lds > attr_lds) {
-        M2M_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_lds = lds;
-    }
     // Fast-form embedding workgroups go FIRST (every CU is free then: ~100 of them run beside the first tower workgroups and
     // are gone after ~15 us; dispatched last they queue on the 16 CUs that 240 one-per-CU tower workgroups leave free and the
     // launch's end depends on where those land: 101-121 us measured from box to box, against a steady ~95 us).
-    static const int embed_first = wgrad_env("M2M_EMBED_FIRST", 1);
+    static const int embed_first = m2m_env_int("M2M_EMBED_FIRST", 1);
     if (ea.fast && n_embed_wgs && embed_first) { a.n_embed_first = n_embed_wgs; a.n_embed_pad = (n_embed_wgs + 7) & ~7; n_embed_wgs = 0; }
     // slot reductions deferred to this launch (towers flagged M2M_WGRAD_REDUCES_SMALL whose backward used slots): up to three
     // ride here, more get the reduction launch of their own
@@ -772,12 +748,9 @@ static int launch_wgrad_group(const m2m_tower* const* host, const m2m_tower* con
     }
     for (int i = 0; i < ra.ntow; ++i) a.reduce_sets = ra.t[i].nlaunch > a.reduce_sets ? ra.t[i].nlaunch : a.reduce_sets;
     a.n_reduce = SPR_NBX * a.reduce_sets * ra.ntow;
-    hipLaunchKernelGGL(kern, dim3((unsigned)(a.n_embed_pad + a.n_tower_wgs + n_embed_wgs + a.n_reduce)), dim3(KG::THREADS), lds, st, a, ea, ra);
-    M2M_CHECK_HIP(hipGetLastError());
-    return 0;
+    return m2m_launch<tower_wgrad_group_kernel<P, D, RCDM>>(dim3((unsigned)(a.n_embed_pad + a.n_tower_wgs + n_embed_wgs + a.n_reduce)), dim3(KG::THREADS),
+                                                            lds, lds, st, a, ea, ra);
 }
-
-int m2m_check_tower(const m2m_tower* t, int B);
 
 // 1 if m2m_towers_wgrad on these towers at batch B leaves part of tower i's channel-mixing gradients in its slot (bit i of the
 // result): the caller must then add the slot (m2m_adam_step_ranges / m2m_wgrad_fold) before using the gradient.
@@ -802,19 +775,14 @@ extern "C" int m2m_tower_wgrad(const m2m_tower* t, int B, uint32_t seed, uint32_
             if (int rc = m2m_split_small_grads(one, st)) return rc;
         }
     }
-    if (m2m_wgrad_recompute(t, B)) {
-        if (m2m_drop_mode(1, t->p_drop) == DM_HALF) return launch_wgrad<PREC_BF16, 128, DM_HALF>(t, B, seed, step, step_dev, st);
-        return launch_wgrad<PREC_BF16, 128, DM_NONE>(t, B, seed, step, step_dev, st);
-    }
-#define M2M_WG_CASE(PP, DD) if (t->prec == PP && t->D == DD) return launch_wgrad<PP, DD, -1>(t, B, seed, step, step_dev, st);
-    M2M_WG_CASE(PREC_BF16, 32) M2M_WG_CASE(PREC_BF16, 64) M2M_WG_CASE(PREC_BF16, 128) M2M_WG_CASE(PREC_BF16, 256)
-    M2M_WG_CASE(PREC_F32, 32) M2M_WG_CASE(PREC_F32, 64) M2M_WG_CASE(PREC_F32, 128) M2M_WG_CASE(PREC_F32, 256)
-#undef M2M_WG_CASE
+    if (m2m_wgrad_recompute(t, B))      // bf16, hidden_dim 128, dropout off or p == 0.5
+        return m2m_dispatch<DM_NONE, DM_HALF>(m2m_drop_mode(1, t->p_drop), -1, [&](auto DM) { return launch_wgrad<PREC_BF16, 128, DM()>(t, B, seed, step, step_dev, st); });
+    const int rc = m2m_dispatch_pd(m2m_wide_dims{}, t->prec, t->D, [&](auto P, auto D) { return launch_wgrad<P(), D(), -1>(t, B, seed, step, step_dev, st); });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("tower_wgrad: unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }
 
-extern "C" int m2m_heads_part_tiles(int B);
 static int towers_wgrad_impl(const m2m_tower* const* towers, const m2m_tower* const* dev_towers, int ntowers,
                              const m2m_embed* const* embeds, const float* const* inputs, const float* const* d_x0s,
                              const m2m_tower* const* embed_towers, int nembeds,
@@ -870,15 +838,14 @@ static int towers_wgrad_impl(const m2m_tower* const* towers, const m2m_tower* co
         m2m_set_error("towers_wgrad_tail: the recompute form READS the dropout counter in this launch; advance it with m2m_counter_add", __FILE__, __LINE__);
         return -1;
     }
-    if (m2m_wgrad_recompute(t, B)) {
-        if (m2m_drop_mode(1, t->p_drop) == DM_HALF)
-            return launch_wgrad_group<PREC_BF16, 128, DM_HALF>(towers, dev_towers, ntowers, embeds, inputs, d_x0s, embed_towers, nembeds, B, seed, step, step_dev, st, heads_reduce);
-        return launch_wgrad_group<PREC_BF16, 128, DM_NONE>(towers, dev_towers, ntowers, embeds, inputs, d_x0s, embed_towers, nembeds, B, seed, step, step_dev, st, heads_reduce);
-    }
-#define M2M_WGG_CASE(PP, DD) if (t->prec == PP && t->D == DD) return launch_wgrad_group<PP, DD, -1>(towers, dev_towers, ntowers, embeds, inputs, d_x0s, embed_towers, nembeds, B, seed, step, step_dev, st, heads_reduce, bump_counter);
-    M2M_WGG_CASE(PREC_BF16, 32) M2M_WGG_CASE(PREC_BF16, 64) M2M_WGG_CASE(PREC_BF16, 128) M2M_WGG_CASE(PREC_BF16, 256)
-    M2M_WGG_CASE(PREC_F32, 32) M2M_WGG_CASE(PREC_F32, 64) M2M_WGG_CASE(PREC_F32, 128) M2M_WGG_CASE(PREC_F32, 256)
-#undef M2M_WGG_CASE
+    if (m2m_wgrad_recompute(t, B))
+        return m2m_dispatch<DM_NONE, DM_HALF>(m2m_drop_mode(1, t->p_drop), -1, [&](auto DM) {
+            return launch_wgrad_group<PREC_BF16, 128, DM()>(towers, dev_towers, ntowers, embeds, inputs, d_x0s, embed_towers, nembeds, B, seed, step, step_dev, st, heads_reduce);
+        });
+    const int rc = m2m_dispatch_pd(m2m_wide_dims{}, t->prec, t->D, [&](auto P, auto D) {
+        return launch_wgrad_group<P(), D(), -1>(towers, dev_towers, ntowers, embeds, inputs, d_x0s, embed_towers, nembeds, B, seed, step, step_dev, st, heads_reduce, bump_counter);
+    });
+    if (rc != M2M_NO_BUILD) return rc;
     m2m_set_error("towers_wgrad: unsupported (prec, D)", __FILE__, __LINE__);
     return -1;
 }
@@ -926,8 +893,7 @@ extern "C" int m2m_wgrad_fold(const m2m_tower* t, void* stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const long n = 2L * t->C * t->D + t->C;
     for (int b = 0; b < t->nblocks; ++b) {
-        hipLaunchKernelGGL(wgrad_fold_kernel, dim3(512), dim3(256), 0, st, t->blk[b].g_ch_w1, t->wslot[b], n);
-        M2M_CHECK_HIP(hipGetLastError());
+        if (int rc = m2m_launch<wgrad_fold_kernel>(dim3(512), dim3(256), 0, 0, st, t->blk[b].g_ch_w1, t->wslot[b], n)) return rc;
     }
     return 0;
 }

@@ -736,6 +736,7 @@ def _builds_of(case):
 
 def test_shape_envelope_covers_every_build():
     from shape_cases import CASES, LDS_EDGE
+    # what the library builds is named once, in m2_mixer_amd/csrc/dispatch.h (m2m_precs, m2m_fused_dims, m2m_wide_dims, m2m_drop_modes)
     builds = set()
     for prec in ("fp32", "bf16"):
         for dm in ("none", "half", "gen"):
