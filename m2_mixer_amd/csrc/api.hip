@@ -161,12 +161,6 @@ extern "C" int m2m_pack_tower(const m2m_tower* t, void* stream) {
 // five launches forked over side streams).  Grid layout: see pack_all_kernel.
 #define M2M_PACK_TOWERS 3
 #define M2M_PACK_EMBEDS 2
-#ifndef M2M_W1TC_SKIP
-#define M2M_W1TC_SKIP 1
-#endif
-#ifndef M2M_PACK_NT_DEFAULT
-#define M2M_PACK_NT_DEFAULT 0
-#endif
 struct PackAllArgs {
     m2m_tower4 tw[M2M_PACK_TOWERS];
     m2m_embed em[M2M_PACK_EMBEDS];
@@ -182,7 +176,7 @@ struct PackAllArgs {
 // path, which needs the tower's slab buffer.  Such towers skip the copy in the whole-model re-pack (8.4 MB of 100 MB on
 // M2-Mixer-B).  m2m_pack_tower / m2m_pack (per-tower, tests, the module path) always write all copies.
 static inline int pack_skips_w1tc(const m2m_tower* t) {
-    return t->prec == PREC_BF16 && t->D == 128 && !m2m_is_wide(t) && t->slabs == nullptr && M2M_W1TC_SKIP;
+    return t->prec == PREC_BF16 && t->D == 128 && !m2m_is_wide(t) && t->slabs == nullptr;
 }
 extern "C" int m2m_pack_skips_w1tc(const m2m_tower* t) { return t ? pack_skips_w1tc(t) : 0; }
 static_assert(sizeof(PackAllArgs) <= 4096, "kernel arguments are limited to 4 KiB");
@@ -318,7 +312,7 @@ extern "C" int m2m_pack_all(const m2m_tower* const* towers, int ntowers, const m
     PackAllArgs a;
     memset(&a, 0, sizeof(a));
     a.nt = ntowers; a.ne = nembeds;
-    static const int pack_nt = m2m_env_int("M2M_PACK_NT", M2M_PACK_NT_DEFAULT);
+    static const int pack_nt = m2m_env_int("M2M_PACK_NT", 0);
     a.nt_loads = pack_nt;
     int prec = -1, tiles = 0, maxD = 0;
     for (int i = 0; i < M2M_PACK_TOWERS; ++i) {
@@ -390,9 +384,6 @@ static __device__ __forceinline__ void adam_one(const AdamK& k, float g, float& 
 // so what the chain kernels keep there (weights, the stored operands of the last backward blocks: m2m_handoff_resident_blocks)
 // survives the optimizer's 230 MB.  1: exp_avg / exp_avg_sq (read once, written once per step), 2: parameter loads,
 // 4: parameter stores (the re-pack then reads the parameters from HBM), 8: gradient loads.
-#ifndef M2M_ADAM_NT_DEFAULT
-#define M2M_ADAM_NT_DEFAULT 1
-#endif
 template <bool ON> static __device__ __forceinline__ float ld_maybe_nt(const float* p) { return ON ? __builtin_nontemporal_load(p) : *p; }
 template <bool ON> static __device__ __forceinline__ void st_maybe_nt(float* p, float v) { if (ON) __builtin_nontemporal_store(v, p); else *p = v; }
 template <bool LOWP, int NT>
@@ -485,7 +476,7 @@ static int adam_launch(float* param, float* grad, const void* grad_bf16, float* 
     auto launch = [&](float* p_, float* g_, const unsigned short* gb_, float* m_, float* v_, long n_, const AdamRanges& r_) {
         long grid = ceil_div(n_, 1024);
         if (grid > 2048) grid = 2048;
-        static const int nt = m2m_env_int("M2M_ADAM_NT", M2M_ADAM_NT_DEFAULT);
+        static const int nt = m2m_env_int("M2M_ADAM_NT", 1);
 #define M2M_ADAM_GO(LP, N) hipLaunchKernelGGL((adam_kernel<LP, N>), dim3((unsigned)grid), dim3(256), 0, st, p_, g_, gb_, m_, v_, n_, state, beta1, beta2, \
                                               eps, weight_decay, grad_scale, r_)
 #define M2M_ADAM_SW(LP) switch (nt) { case 1: M2M_ADAM_GO(LP, 1); break; case 3: M2M_ADAM_GO(LP, 3); break; case 7: M2M_ADAM_GO(LP, 7); break; \
@@ -589,9 +580,6 @@ static __device__ __forceinline__ AdamStreams adam_streams(const AdamPackPlan& p
 // stores -- their loads are clamped duplicates): EVERY load first, then the arithmetic, then the stores.  The first version of
 // this kernel updated element by element through generic pointers (load, store, load ... in series; the stores may alias the
 // next loads): 97 us for the model against 45 + 19 us for the flat Adam + m2m_pack_all it was meant to replace.
-#ifndef M2M_AP_NT_P
-#define M2M_AP_NT_P 0
-#endif
 // NTMV (compile time -- a run-time choice between a plain and a non-temporal store of the same value is merged into ONE plain
 // store by the compiler): exp_avg / exp_avg_sq past the memory-side cache (large models, see adam_kernel's NT)
 template <bool LOWP, int NV, bool NTMV = false>
@@ -601,8 +589,7 @@ static __device__ __forceinline__ void adam_vec(const AdamStreams& s, const Adam
     f32x4_t gv[NV], mv[NV], vv[NV], av[NV];
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
-        // (the big masters too when M2M_AP_NT_P: in the one-launch form nothing re-reads them before the next step's Adam)
-        if constexpr (NTMV && M2M_AP_NT_P) pn[k] = __builtin_nontemporal_load((g4_t)(s.p + off[k])); else pn[k] = *(g4_t)(s.p + off[k]);
+        pn[k] = *(g4_t)(s.p + off[k]);          // (the masters stay plain: DESIGN.md, "Retired compile-time experiments")
         if constexpr (NTMV) { mv[k] = __builtin_nontemporal_load((g4_t)(s.m + off[k])); vv[k] = __builtin_nontemporal_load((g4_t)(s.v + off[k])); }
         else { mv[k] = *(g4_t)(s.m + off[k]); vv[k] = *(g4_t)(s.v + off[k]); }
         if (LOWP) {
@@ -623,7 +610,7 @@ static __device__ __forceinline__ void adam_vec(const AdamStreams& s, const Adam
 #pragma unroll
     for (int k = 0; k < NV; ++k)
         if (ok[k]) {
-            if constexpr (NTMV && M2M_AP_NT_P) __builtin_nontemporal_store(pn[k], (g4_t)(s.p + off[k])); else *(g4_t)(s.p + off[k]) = pn[k];
+            *(g4_t)(s.p + off[k]) = pn[k];
             if constexpr (NTMV) { __builtin_nontemporal_store(mv[k], (g4_t)(s.m + off[k])); __builtin_nontemporal_store(vv[k], (g4_t)(s.v + off[k])); }
             else { *(g4_t)(s.m + off[k]) = mv[k]; *(g4_t)(s.v + off[k]) = vv[k]; }
             if (!s.keep) *(g4_t)(s.g + off[k]) = f32x4_t{0.f, 0.f, 0.f, 0.f};
@@ -708,9 +695,7 @@ static __device__ __forceinline__ void adam_pack_tile(const AdamPackPlan& pl, co
 // (32 rows of W1 are one contiguous 32 x D chunk) and W2 is walked in tiles of 8 rows x AP_W columns (2 KiB runs): a packed NAT slot
 // of W2^T is eight consecutive d of one column -- exactly the tile's eight rows --, a packed CHN slot of W2 eight columns of one
 // row, so both images come out of the tile (128- and 256-byte runs of 16-byte slots).
-#ifndef AP_W
 #define AP_W 512
-#endif
 template <int P, bool LOWP, int DD, bool NTMV>
 static __device__ __forceinline__ void adam_pack_w1_tile(const AdamPackPlan& pl, const AdamConsts& c, const m2m_tower4& tw, int block, int q, char* smem, bool skip_w1tc) {
     const m2m_block& k = tw.blk[block];

@@ -199,23 +199,6 @@ static __device__ __forceinline__ gtab_t pwl_cell(int i, float scale) {
 static __device__ __forceinline__ void gelu_tab_fill(gtab_t* tab, float scale, int tid, int nthreads) {
     for (int k = tid; k < GELU_TAB_N; k += nthreads) tab[k] = pwl_cell(k, scale);
 }
-// gelu(x) * scale and gelu'(x) * scale, `scale` being the value the table was filled with (bf16) / applied here (fp32)
-// Closed form (ActB below): Phi(x) through the Abramowitz-Stegun 7.1.26 erfc polynomial (|err| <
-// 1e-7), one v_exp + one v_rcp + ~13 plain VALU for gelu AND gelu' (they share exp(-x^2/2)); no LDS traffic: the table costs
-// one ds_read_b128 at a random address per element, ~16 LDS cycles per wave-instruction with its bank conflicts.
-static __device__ __forceinline__ void gelu_grad_as(float x, float& g, float& dg) {
-    const float e = __builtin_amdgcn_exp2f(x * x * -0.72134752044448170368f);       // exp(-x^2 / 2)
-    const float t = __builtin_amdgcn_rcpf(__builtin_fmaf(__builtin_fabsf(x), 0.23164189213f, 1.0f));   // 1 / (1 + p |x| / sqrt 2)
-    float p = 0.5f * 1.061405429f;
-    p = __builtin_fmaf(p, t, 0.5f * -1.453152027f);
-    p = __builtin_fmaf(p, t, 0.5f * 1.421413741f);
-    p = __builtin_fmaf(p, t, 0.5f * -0.284496736f);
-    p = __builtin_fmaf(p, t, 0.5f * 0.254829592f);
-    const float q = p * t * e;                                                      // Phi(-|x|)
-    const float cdf = x >= 0.f ? 1.0f - q : q;
-    g = x * cdf;
-    dg = __builtin_fmaf(x * e, 0.3989422804014327f, cdf);
-}
 // Forward-only table: {a, b} per cell (8 bytes).  The forward never needs gelu', and an 8-byte read at a random address
 // conflicts far less than a 16-byte one (two 32-lane groups over 64 banks instead of four 16-lane groups of four banks each).
 typedef __attribute__((ext_vector_type(2))) float gtab2_t;
@@ -247,6 +230,7 @@ static __device__ __forceinline__ void gelu_grad_tabh(const gtabh_t* tab, float 
     g = __builtin_fmaf((float)e[1], x, (float)e[0]);
     dg = __builtin_fmaf((float)e[3], x, (float)e[2]);
 }
+// gelu(x) * scale and gelu'(x) * scale, `scale` being the value the table was filled with (bf16) / applied here (fp32)
 template <int P> struct Act;
 template <> struct Act<PREC_BF16> {
     static constexpr bool USES_TABLE = true;
@@ -278,56 +262,8 @@ template <> struct Act<PREC_F32> {
         gelu_grad_scaled(static_cast<const gtab_t*>(nullptr), x, scale, g, dg);
     }
 };
-// The activation as the BACKWARD kernels evaluate it: the table too (M2M_BWD_FORMULA=1 selects the closed form).  Measured in
-// one process both ways: while the backward column loop still carried ~70 wasted packing instructions per step the closed form
-// won by 3-4 % (less LDS traffic); once those were gone the loop was VALU-issue-bound and the table's fewer instructions win
-// by 2 % on the step (932k vs 915k samples/s).  The forward chains always preferred the table (closed form: +4 % time).
-#ifndef M2M_BWD_FORMULA
-#define M2M_BWD_FORMULA 0
-#endif
-template <int P> struct ActB : Act<P> {};
-#if M2M_BWD_FORMULA
-template <> struct ActB<PREC_BF16> {
-    static constexpr bool USES_TABLE = false;
-    static __device__ __forceinline__ void gelu_grad_scaled(const gtab_t*, float x, float scale, float& g, float& dg) {
-        gelu_grad_as(x, g, dg);
-        g *= scale;
-        dg *= scale;
-    }
-    static __device__ __forceinline__ void gelu_grad_scaled(const gtabh_t*, float x, float scale, float& g, float& dg) {
-        gelu_grad_scaled(static_cast<const gtab_t*>(nullptr), x, scale, g, dg);
-    }
-};
-#endif
-// Table type of the backward chain kernel (tower_bwd.hip, token_mfma.h's backward): the packed fp16 table (M2M_BWD_HTAB=0: fp32).
-#ifndef M2M_BWD_HTAB
-#define M2M_BWD_HTAB 1
-#endif
-#if M2M_BWD_HTAB
-typedef gtabh_t gtabB_t;
-static __device__ __forceinline__ void gelu_tabB_fill(gtabB_t* tab, float scale, int tid, int nthreads) { gelu_tabh_fill(tab, scale, tid, nthreads); }
-#else
-typedef gtab_t gtabB_t;
-static __device__ __forceinline__ void gelu_tabB_fill(gtabB_t* tab, float scale, int tid, int nthreads) { gelu_tab_fill(tab, scale, tid, nthreads); }
-#endif
-// The activation inside the token-mixing MFMA phases (token_mfma.h): 1 = closed form, 0 = table.  M2M_TOK_FORMULA bit 0: forward,
-// bit 1: backward.
-#ifndef M2M_TOK_FORMULA
-#define M2M_TOK_FORMULA 0
-#endif
-struct ActTokF {
-    static __device__ __forceinline__ float gelu_scaled(const gtab2_t* tab, float x, float scale) {
-        if (M2M_TOK_FORMULA & 1) { float g, dg; gelu_grad_as(x, g, dg); return g * scale; }
-        return Act<PREC_BF16>::gelu_scaled(tab, x, scale);
-    }
-};
-struct ActTokB {
-    template <class TAB>
-    static __device__ __forceinline__ void gelu_grad_scaled(const TAB* tab, float x, float scale, float& g, float& dg) {
-        if (M2M_TOK_FORMULA & 2) { gelu_grad_as(x, g, dg); g *= scale; dg *= scale; }
-        else ActB<PREC_BF16>::gelu_grad_scaled(tab, x, scale, g, dg);
-    }
-};
+// The backward chain kernels (tower_bwd.hip, token_mfma.h's backward) evaluate the activation through Act too, from the packed
+// fp16 table gtabh_t.  (Closed form, fp32 table: DESIGN.md, "Retired compile-time experiments".)
 // 0 / ~0 from bit k of w (v_bfe_i32): keep-masks are applied with one AND
 static __device__ __forceinline__ unsigned int bit_to_mask(unsigned int w, int k) {
     return (unsigned int)(((int)(w << (31 - k))) >> 31);

@@ -11,9 +11,7 @@
 #include <stddef.h>
 #include <string.h>
 
-#ifndef BM
 #define BM 16                      // token rows per workgroup of the chain kernels (16 or 32)
-#endif
 #define MT (BM / 16)
 #define NTHREADS 512
 #define NWAVES 8
@@ -109,9 +107,7 @@ static __device__ __forceinline__ bool drop_keep_elem(const Drop& d, unsigned in
 // bf16, one tile in fp32): npair 2-KiB blocks plus a pad.  Without the pad the stride is a power of two (128 KiB at batch
 // 512), every column slice of the weight-gradient launch walks its stream in lockstep, and all of them hit the same L2
 // channel at the same time.
-#ifndef M2M_HCHN_PAD
 #define M2M_HCHN_PAD 2304
-#endif
 static __host__ __device__ __forceinline__ long m2m_hchn_stride(long npair) { return npair * 2048 + M2M_HCHN_PAD; }
 
 // A tower descriptor with room for 4 blocks only: two of them (plus per-tower arguments) fit the 4 KiB kernel-argument

@@ -123,7 +123,7 @@ static __device__ __forceinline__ void token_fwd_mfma(const float* ub, float* xs
             for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const float v = ActTokF::gelu_scaled(gtab, hacc[u][tt][r], scale_th);
+                    const float v = Act<PREC_BF16>::gelu_scaled(gtab, hacc[u][tt][r], scale_th);
                     hacc[u][tt][r] = DM == DM_NONE ? v : mask_f(v, bit_to_mask(word[u], 16 * tt + r));
                 }
         f32x4_t o[TU];
@@ -165,7 +165,7 @@ static __device__ __forceinline__ void token_fwd_mfma(const float* ub, float* xs
 template <int NMAX> struct TokRed { static constexpr int LD = 2 * (NMAX + 1) * 32 + NMAX; };
 
 template <int D, int NMAX, int DM>
-static __device__ __forceinline__ void token_bwd_mfma(float* ub, const float* dov, const float* tokw, const gtabB_t* gtab,
+static __device__ __forceinline__ void token_bwd_mfma(float* ub, const float* dov, const float* tokw, const gtabh_t* gtab,
                                                       const unsigned int* wth, float* red, int N, int ns, float scale_th,
                                                       int wave, int lane) {
     constexpr int XLD = TileGeom<D>::XLD, TW_LD = 2 * NMAX + 4, KS = NMAX / 4, CP = D / 32;
@@ -207,10 +207,7 @@ static __device__ __forceinline__ void token_bwd_mfma(float* ub, const float* do
 
     // PU pairs per pass, stage by stage: one pair alone is a chain of ~10 dependent LDS / MFMA / VALU round trips, and the two
     // waves of a SIMD do not cover it (measured: 3.2 us per pair against 0.8 us of instruction issue)
-#ifndef M2M_TOK_PU
-#define M2M_TOK_PU 1
-#endif
-    constexpr int PU = NMAX == 4 ? M2M_TOK_PU : 1;      // (pairs per pass; NMAX 4: a 16-row tile holds 4 samples = 16 pairs, two per wave.  2 was measured in rounds 2 and 4 (-DM2M_TOK_PU=2): the 64 extra accumulator registers spill around the phase (58 VGPRs), two-tower launch 165 -> 194 us / 120 -> 145 us)
+    constexpr int PU = 1;       // (pairs per pass.  Two for NMAX 4 spilled around the phase: DESIGN.md, "Retired compile-time experiments")
     const int npair = ns * CP;
     for (int p0 = wave; p0 < npair; p0 += NWAVES * PU) {
         int sl[PU], d0[PU];
@@ -247,70 +244,45 @@ static __device__ __forceinline__ void token_bwd_mfma(float* ub, const float* do
             }
         }
         // dH = dG gelu'(H) keep scale, G = gelu(H) keep scale: element (column 16 ct + 4 g + r, hidden unit il + 16 tt)
-        // Staged form (table activation): the 16 cells of a pair are looked up TOGETHER -- indices, all reads, a scheduling barrier,
-        // then the arithmetic.  Written element by element (below), hipcc followed every ds_read_b64 with s_waitcnt lgkmcnt(0):
+        // Staged: the 16 cells of a pair are looked up TOGETHER -- indices, all reads, a scheduling barrier,
+        // then the arithmetic.  Written element by element, hipcc followed every ds_read_b64 with s_waitcnt lgkmcnt(0):
         // 16 exposed LDS round trips per pair, half of this phase's time (the backward kernel sits at its register limit and the
         // scheduler sinks every load to its use; tower_bwd.hip's column loop has the same cure).  The keep-mask is folded into
         // the index (a dropped element reads cell 0 = zeros), as in the column loop.
-        constexpr bool TOK_STAGED = ActB<PREC_BF16>::USES_TABLE && M2M_BWD_HTAB && !(M2M_TOK_FORMULA & 2);
-        if constexpr (TOK_STAGED) {
 #pragma unroll
-            for (int u = 0; u < PU; ++u)
+        for (int u = 0; u < PU; ++u)
 #pragma unroll
-                for (int ct = 0; ct < 2; ++ct) {                             // (8 cells at a time: 16 more registers, no spills)
-                    u32x4_t w4 = u32x4_t{~0u, ~0u, ~0u, ~0u};
-                    if (DM != DM_NONE) w4 = *reinterpret_cast<const u32x4_t*>(wth + sl[u] * D + d0[u] + 16 * ct + 4 * g);
-                    gtabB_t e[2][4];
-                    {
-                        unsigned int idx[2][4];
-#pragma unroll
-                        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                idx[tt][r] = pwl_index(H[u][ct][tt][r]);
-                                if (DM != DM_NONE) idx[tt][r] &= (unsigned int)(((int)(w4[r] << (31 - il - 16 * tt))) >> 31);
-                            }
-#pragma unroll
-                        for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) e[tt][r] = gtab[idx[tt][r]];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
+            for (int ct = 0; ct < 2; ++ct) {                             // (8 cells at a time: 16 more registers, no spills)
+                u32x4_t w4 = u32x4_t{~0u, ~0u, ~0u, ~0u};
+                if (DM != DM_NONE) w4 = *reinterpret_cast<const u32x4_t*>(wth + sl[u] * D + d0[u] + 16 * ct + 4 * g);
+                gtabh_t e[2][4];
+                {
+                    unsigned int idx[2][4];
 #pragma unroll
                     for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            const float x = H[u][ct][tt][r];
-                            const float gl = __builtin_fmaf((float)e[tt][r][1], x, (float)e[tt][r][0]);
-                            const float dgl = __builtin_fmaf((float)e[tt][r][3], x, (float)e[tt][r][2]);
-                            dG[u][ct][tt][r] *= dgl;
-                            H[u][ct][tt][r] = gl;
+                            idx[tt][r] = pwl_index(H[u][ct][tt][r]);
+                            if (DM != DM_NONE) idx[tt][r] &= (unsigned int)(((int)(w4[r] << (31 - il - 16 * tt))) >> 31);
                         }
-                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int tt = 0; tt < 2; ++tt)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) e[tt][r] = gtab[idx[tt][r]];
                 }
-        } else {
-#pragma unroll
-        for (int u = 0; u < PU; ++u)
-#pragma unroll
-            for (int ct = 0; ct < 2; ++ct) {
-                u32x4_t w4 = u32x4_t{~0u, ~0u, ~0u, ~0u};
-                if (DM != DM_NONE) w4 = *reinterpret_cast<const u32x4_t*>(wth + sl[u] * D + d0[u] + 16 * ct + 4 * g);
+                __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        float gl, dgl;
-                        ActTokB::gelu_grad_scaled(gtab, H[u][ct][tt][r], scale_th, gl, dgl);
-                        const float v = dG[u][ct][tt][r] * dgl;
-                        if (DM == DM_NONE) { dG[u][ct][tt][r] = v; H[u][ct][tt][r] = gl; }
-                        else {
-                            const unsigned int mk = (unsigned int)(((int)(w4[r] << (31 - il - 16 * tt))) >> 31);
-                            dG[u][ct][tt][r] = mask_f(v, mk);
-                            H[u][ct][tt][r] = mask_f(gl, mk);
-                        }
+                        const float x = H[u][ct][tt][r];
+                        const float gl = __builtin_fmaf((float)e[tt][r][1], x, (float)e[tt][r][0]);
+                        const float dgl = __builtin_fmaf((float)e[tt][r][3], x, (float)e[tt][r][2]);
+                        dG[u][ct][tt][r] *= dgl;
+                        H[u][ct][tt][r] = gl;
                     }
+                __builtin_amdgcn_sched_barrier(0);
             }
-        }
         Frag hB[PU][2];                                                      // k = the pair's 32 columns (chained), j = t
 #pragma unroll
         for (int u = 0; u < PU; ++u) {

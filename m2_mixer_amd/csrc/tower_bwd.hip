@@ -44,7 +44,7 @@ template <int P, int D, int NMAX, int TG> struct BwdLds {
     static constexpr int RED_LD = RED_LD0 > TokRed<NM>::LD ? RED_LD0 : TokRed<NM>::LD;
     static constexpr int PB = 4 * D + (TOK ? 32 * TW_LD : 0);                  // floats of one block's small parameters
     static constexpr size_t FIXED = (size_t)BM * XLD * sizeof(float) * (1 + RowSlabs<D>::N + 2) + 2 * (size_t)BM * D * Prec<P>::ESZ +
-                                    GELU_TAB_N * sizeof(gtabB_t) + (TOK ? (size_t)NWAVES * RED_LD * sizeof(float) : 0);
+                                    GELU_TAB_N * sizeof(gtabh_t) + (TOK ? (size_t)NWAVES * RED_LD * sizeof(float) : 0);
     // + keep-words of the token-hidden site (one per column of the workgroup's SPW = BM / N samples) + hidden bias of one block
     static size_t bytes(int nblocks, int N, int Cp) {
         return FIXED + (TOK ? (size_t)(BM / N) * D * sizeof(unsigned int) : 0) + (size_t)nblocks * PB * sizeof(float) +
@@ -57,17 +57,7 @@ template <int P, int D, int NMAX, int TG> struct BwdLds {
 #define M2M_LDS_MAX 163840
 #endif
 
-// the small parameter gradients' float atomics (M2M_ABL_NOATOM: timing ablation, drops them)
-#ifdef M2M_ABL_NOATOM
-#define M2M_SMALL_ATOMIC(p, v) asm volatile("" :: "v"(p), "v"(v))
-#else
-#define M2M_SMALL_ATOMIC(p, v) atomicAdd(p, v)
-#endif
 TIMER_DECL(g_tm_bwd);
-// occupancy the scheduler plans for (see the kernels' declarations)
-#ifndef M2M_BWD_KATTR
-#define M2M_BWD_KATTR
-#endif
 __device__ int g_bwd_static_split = 1;      // 1: static split of the bf16 column loop (default), 0: ticket counter (M2M_BWD_TICKETS=1)
 // copies the environment's choice to the device once per process (before the first backward launch on any stream)
 static int bwd_split_mode_init(hipStream_t st) {
@@ -123,7 +113,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
     float* ta = tdy + TILE_F;                            // A = LN2(x_mid) (fp32)
     char* at = reinterpret_cast<char*>(ta + TILE_F);
     char* dyp = at + IMG_B;
-    gtabB_t* gtab = reinterpret_cast<gtabB_t*>(dyp + IMG_B);     // [GELU_TAB_N] (bf16 mode only)
+    gtabh_t* gtab = reinterpret_cast<gtabh_t*>(dyp + IMG_B);     // [GELU_TAB_N] (bf16 mode only)
     float* red = reinterpret_cast<float*>(gtab + GELU_TAB_N);    // [NWAVES][RED_LD] (token path)
     unsigned int* wth = reinterpret_cast<unsigned int*>(red + (TOK ? NWAVES * RED_LD : 0));   // [BM * D] (token path)
     float* par = reinterpret_cast<float*>(wth + (TOK ? (BM / tw.N) * D : 0));                 // [nblocks][PB]
@@ -295,7 +285,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
             }
         }
     }
-    if (ActB<P>::USES_TABLE) gelu_tabB_fill(gtab, make_drop(true, tw.p_drop, 0u, 0u, 0u).scale, tid, NTHREADS);
+    if (Act<P>::USES_TABLE) gelu_tabh_fill(gtab, make_drop(true, tw.p_drop, 0u, 0u, 0u).scale, tid, NTHREADS);
 #pragma unroll
     for (int b = 0; b < MAXB; ++b)
         if (b < tw.nblocks) {
@@ -339,13 +329,13 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
 #pragma unroll 4
             for (int r = 0; r < BM; ++r) s_ += src[r * XLD + c];
             if (store) (d < D ? gw : gb)[c] = s_;                 // gw / gb point into this workgroup's slot
-            else M2M_SMALL_ATOMIC((d < D ? gw : gb) + c, s_);
+            else atomicAdd((d < D ? gw : gb) + c, s_);
         }
     };
     // Small parameter gradients without atomics (`part` != NULL): every workgroup STORES its partial sums into its own slot
     // (split.h's layout; slot set 0 = the final LayerNorm, slot set nblocks - b = block b) and one reduction launch adds the
     // slots to the gradients in a fixed order.  256 workgroups adding to the same ~3000 addresses ran at the contended-atomic
-    // rate: 16 us of the step's two backward launches (timing ablation M2M_ABL_NOATOM), and order-dependent sums.
+    // rate: 16 us of the step's two backward launches (timing ablation without them), and order-dependent sums.
     auto slot_of = [&](int b) -> float* { return PART ? reinterpret_cast<float*>(slotp[tw.nblocks - b]) : nullptr; };
     for (int b = tw.nblocks - 1; b >= 0; --b) {
         const m2m_block& bk = tw.blk[b];
@@ -433,7 +423,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
 #pragma unroll 4
             for (int r = 0; r < BM; ++r) s_ += tdy[r * XLD + d];
             if constexpr (PART) sl_b2[SPP_B2(D) + d] = s_;
-            else M2M_SMALL_ATOMIC(reinterpret_cast<float*>((char*)p_gb2) + d, s_);
+            else atomicAdd(reinterpret_cast<float*>((char*)p_gb2) + d, s_);
         }
         pack_tile_chn_t<P, D>(tdy, (char*)p_dyt + pair_off, tile_in_pair, tb1);
         pack_tile_chn_t<P, D>(ta, (char*)p_atc + pair_off, tile_in_pair, tb1);
@@ -470,13 +460,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
         // registers are free.  Rows are XOR-swizzled by 16-byte chunk (chunk ^ (((row & 3) << 2) | ((row >> 2) & 3))) so that
         // both the 16-byte fragment writes and the 8-byte transposed reads spread over the banks.  The slot lies inside the
         // wave's own slab (dead until the wave leaves the loop).
-#ifndef M2M_W1LDS
-#define M2M_W1LDS 1
-#endif
-#ifndef M2M_TICKETS
-#define M2M_TICKETS 1
-#endif
-        constexpr bool W1LDS = M2M_W1LDS && D == 128 && P == PREC_BF16;      // (256-byte rows: hidden_dim 128)
+        constexpr bool W1LDS = D == 128 && P == PREC_BF16;      // (256-byte rows: hidden_dim 128)
         char* w1slot = reinterpret_cast<char*>(slabs + wave * TILE_F);
         // physical chunk = logical chunk ^ swz(row), swz(r) = (r & 7) | ((r & 1) << 3): its low three bits are a bijection of
         // r & 7 (the 8 lanes one ds_write_b128 cycle serves are 8 consecutive rows at one logical chunk: 8 distinct chunks mod
@@ -496,26 +480,9 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
         // Default since round 3: the STATIC split (g_bwd_static_split = 1): the column sums of dA have a fixed order.  The ticket
         // counter (M2M_BWD_TICKETS=1 in the environment, read before the first launch) gained 2.6 % in round 2; in round 3, with
         // the small-gradient atomics gone, three A/B runs on three boxes showed no difference.
-        constexpr bool TICKETS_CT = P == PREC_BF16 && M2M_TICKETS;
+        constexpr bool TICKETS_CT = P == PREC_BF16;
         const bool TICKETS = TICKETS_CT && __builtin_amdgcn_readfirstlane(g_bwd_static_split) == 0;
-        // The two waves of a SIMD (w and w + 4) run the same program and leave the barrier before the loop together: their MFMA
-        // clusters and their VALU epilogues would collide.  M2M_STAGGER delays waves 4-7 by about half a step (s_sleep counts 64
-        // cycles) so that one wave's matrix work lies beside its partner's vector work; with tickets the delayed waves simply
-        // draw fewer steps, the stagger costs nothing at the end.  M2M_PRIO_STATIC: the younger half at priority 1 for the
-        // loop; M2M_PRIO_FLIP: priority 1 around each step's MFMA cluster.
-#ifndef M2M_STAGGER
-#define M2M_STAGGER 0
-#endif
-#ifndef M2M_PRIO_STATIC
-#define M2M_PRIO_STATIC 0
-#endif
-#ifndef M2M_PRIO_FLIP
-#define M2M_PRIO_FLIP 0
-#endif
-        if (TICKETS && (M2M_STAGGER > 0 || M2M_PRIO_STATIC) && __builtin_amdgcn_readfirstlane(wave) >= NWAVES / 2) {
-            if (M2M_PRIO_STATIC) __builtin_amdgcn_s_setprio(1);
-            if (M2M_STAGGER > 0) __builtin_amdgcn_s_sleep(M2M_STAGGER);
-        }
+        // (Staggered halves, wave priorities around the loop or its MFMA clusters: DESIGN.md, "Retired compile-time experiments".)
         TIMER_CRESET();
         // ---- staged form of the step (round 4; bf16, hidden_dim 128, table activation) -----------------------------------
         // The ISA of the plain form below showed every one of a step's 16 table look-ups (ds_read_b64) and every one of the third
@@ -528,10 +495,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
         // the table reads, all 16 table reads in flight together, the third product's 16 transposed reads and the next step's
         // bias requested before the transposing MFMAs / packs / stores and consumed after them.  Arithmetic and summation order
         // are those of the plain form (bit-identical results).
-#ifndef M2M_BWD_STAGED
-#define M2M_BWD_STAGED 1
-#endif
-        constexpr bool STAGED = M2M_BWD_STAGED && HOLD && W1LDS && MT == 1 && ActB<P>::USES_TABLE && M2M_BWD_HTAB && NF == 1;
+        constexpr bool STAGED = HOLD && W1LDS && MT == 1 && Act<P>::USES_TABLE && NF == 1;
         f32x4_t bias_n[2] = {f32x4_t{0.f, 0.f, 0.f, 0.f}, f32x4_t{0.f, 0.f, 0.f, 0.f}};      // hidden bias of the step about to run
         if constexpr (STAGED) {
             const int q0 = min(TICKETS ? (int)__builtin_amdgcn_readfirstlane(wave) : wave, npairs - 1);
@@ -556,17 +520,8 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
 #pragma unroll
                     for (int kb = 0; kb < KD; ++kb)
                         *reinterpret_cast<u32x4_t*>(w1_wr + 4096 * t + 16 * ((4 * kb) ^ (swz_w & 12))) = w1f[t][kb].u;
-                // The next step's fragments are requested k-block by k-block right behind the four MFMAs that read this step's (an MFMA
-                // takes its operands when it issues; the load lands hundreds of cycles later): the texture addresser takes 16 cycles
-                // per 1 KiB load, the matrix pipe 16 per MFMA -- the loads' issue (which blocks the in-order wave while the
-                // addresser's queue is full: 490 cycles as one burst behind the products) lies under the products, and the prefetch
-                // distance grows by the length of this stage.  MEASURED (three interleaved repetitions in one process): no gain,
-                // 0.5074-0.5120 against 0.5066-0.5079 ms per step for the burst in two halves (stages B1 / B3) -- with the
-                // round trips gone the loop runs at ~72 % of the texture addresser's rate (18 KiB per wave and step at 64 B/clk:
-                // 2300 of ~3200 cycles per round) and the waves queue behind each other whatever the order.  Off.
-#ifndef M2M_BWD_PF_INTERLEAVE
-#define M2M_BWD_PF_INTERLEAVE 0
-#endif
+                // (The next step's fragments k-block by k-block behind these MFMAs instead of stages B1 / B3: no gain, DESIGN.md,
+                //  "Retired compile-time experiments".)
                 const int qn = __builtin_amdgcn_readfirstlane(TICKETS ? (int)ticket : q + NWAVES);
                 const bool more = qn < npairs;
 #pragma unroll
@@ -577,23 +532,12 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
                     Pr::mma(hacc[1], w1f[1][kb], a);
                     Pr::mma(gacc[0], w2f[0][kb], dy);
                     Pr::mma(gacc[1], w2f[1][kb], dy);
-                    if (M2M_BWD_PF_INTERLEAVE) {
-                        __builtin_amdgcn_sched_barrier(0);
-                        if (more) {
-#pragma unroll
-                            for (int t = 0; t < 2; ++t) {
-                                w1f[t][kb] = ld_frag_global_u(p_w1n, (long)(2 * qn + t) * KD + kb, lane16);
-                                w2f[t][kb] = ld_frag_global_u(p_w2tn, (long)(2 * qn + t) * KD + kb, lane16);
-                            }
-                        }
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 TIMER_CMARK(9);
                 // (B1) first half of the next step's weights (W1: the park writes need it first) + this step's keep-word: both
                 //      independent of the products still in the matrix pipe
-                if (!M2M_BWD_PF_INTERLEAVE && more) {
+                if (more) {
 #pragma unroll
                     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -602,7 +546,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
                 const unsigned int word = drop_hidden_bits<DM>(dr_ch, (unsigned int)(row0 + il), q, Cp) >> (4 * g);
                 __builtin_amdgcn_sched_barrier(0);
                 // (B2) the 16 table cells of this lane's hidden elements: indices, then all reads in flight together
-                gtabB_t e[2][4];
+                gtabh_t e[2][4];
                 {
                     unsigned int idx[2][4];
 #pragma unroll
@@ -619,7 +563,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
                 }
                 __builtin_amdgcn_sched_barrier(0);
                 // (B3) second half of the weight prefetch: its issue lies beside the table reads' latency
-                if (!M2M_BWD_PF_INTERLEAVE && more) {
+                if (more) {
 #pragma unroll
                     for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -710,7 +654,6 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
             }
             TIMER_CMARK(8);    // loop step head: ticket, bias, accumulator init (+ previous step's tail)
             if constexpr (HOLD) {
-            if (M2M_PRIO_FLIP) __builtin_amdgcn_s_setprio(1);
             if constexpr (W1LDS) {
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
@@ -761,7 +704,6 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
             // the MFMAs that still read the current fragments (which would double the live registers).
             __builtin_amdgcn_sched_barrier(0);
             TIMER_CMARK(9);    // wait for this step's weights, W1 park writes, A / dYd fragment reads, products 1-2 issued
-            if (M2M_PRIO_FLIP) __builtin_amdgcn_s_setprio(0);
             Frag w3f[W1LDS ? 1 : NF][W1LDS ? 1 : DT];
             if constexpr (!W1LDS) {
 #pragma unroll
@@ -770,11 +712,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
                 for (int dt = 0; dt < DT; ++dt) w3f[f][dt] = ld_frag_global_u(p_w1tc, (long)(q * NF + f) * DT + dt, lane16);
             }
             const int qn = __builtin_amdgcn_readfirstlane(TICKETS ? (int)ticket : q + NWAVES);
-#ifdef M2M_ABL_NOPF
-            if (false) {
-#else
             if (HOLD && qn < npairs) {
-#endif
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
 #pragma unroll
@@ -794,16 +732,13 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
                         float gl, dgl;                                   // both carry the dropout scale
-#ifdef M2M_ABL_NOGELU
-                        gacc[mt][t][r] *= 0.5f; hacc[mt][t][r] = mask_f(hacc[mt][t][r], bit_to_mask(word, 16 * t + r)); continue;
-#endif
-                        if constexpr (DM != DM_NONE && ActB<P>::USES_TABLE && M2M_BWD_HTAB) {
+                        if constexpr (DM != DM_NONE && Act<P>::USES_TABLE) {
                             gelu_grad_tabh_masked(gtab, hacc[mt][t][r], bit_to_mask(word, 16 * t + r), gl, dgl);
                             gacc[mt][t][r] *= dgl;
                             hacc[mt][t][r] = gl;
                             continue;
                         }
-                        ActB<P>::gelu_grad_scaled(gtab, hacc[mt][t][r], dr_ch.scale, gl, dgl);
+                        Act<P>::gelu_grad_scaled(gtab, hacc[mt][t][r], dr_ch.scale, gl, dgl);
                         const float v = gacc[mt][t][r] * dgl;
                         if (DM == DM_NONE) { gacc[mt][t][r] = v; hacc[mt][t][r] = gl; }
                         else {
@@ -821,7 +756,6 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
             // chained k order) into [m in registers][c across lanes] = exactly the layout that pass consumes, exact in
             // the operand precision.  The MFMA pipe is mostly idle here, so the transpose is nearly free.
             TIMER_CMARK(11);   // epilogue: products 1-2 complete, keep-words, table, chained fragments
-#ifndef M2M_ABL_NOTR
 #pragma unroll
             for (int mt = 0; mt < MT; ++mt) {
                 const int u = BM == 16 ? tile_in_pair : mt;        // 16-row half of the 32-row pair
@@ -850,27 +784,18 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
                 }
                 // streamed out once and read once by the weight-gradient pass: non-temporal, so that the 100 MB per
                 // launch do not evict the weights the other workgroups of this XCD keep re-reading from its L2
-#ifdef M2M_ABL_NOSTORE
-                asm volatile("" :: "v"(od[0]), "v"(od[1]), "v"(oa[0]), "v"(oa[1]));
-                continue;
-#endif
                 if (P == PREC_BF16) {
                     // [column-tile pair q][32-row pair][16-row half u][lane][tile 2q: 4 bf16 | tile 2q+1: 4 bf16]: one full
                     // 16-byte-per-lane store per operand and step (1 KiB contiguous), and the weight-gradient wave that owns
                     // both column tiles reads it back with one 16-byte load per half
                     const long off = (long)q * m2m_hchn_stride(npair) + (pair * 2 + u) * 1024 + lane * 16;
-#ifndef M2M_ST_NT
-#define M2M_ST_NT 1
-#endif
                     const u32x4_t sd = u32x4_t{pack_bf2(od[0][0], od[0][1]), pack_bf2(od[0][2], od[0][3]),
                                                pack_bf2(od[1][0], od[1][1]), pack_bf2(od[1][2], od[1][3])};
-                    if (M2M_ST_NT) __builtin_nontemporal_store(sd, reinterpret_cast<M2M_AS1 u32x4_t*>(p_dh + off));
-                    else *reinterpret_cast<M2M_AS1 u32x4_t*>(p_dh + off) = sd;
+                    __builtin_nontemporal_store(sd, reinterpret_cast<M2M_AS1 u32x4_t*>(p_dh + off));
                     if constexpr (!HREC) {
                         const u32x4_t sa = u32x4_t{pack_bf2(oa[0][0], oa[0][1]), pack_bf2(oa[0][2], oa[0][3]),
                                                    pack_bf2(oa[1][0], oa[1][1]), pack_bf2(oa[1][2], oa[1][3])};
-                        if (M2M_ST_NT) __builtin_nontemporal_store(sa, reinterpret_cast<M2M_AS1 u32x4_t*>(p_h + off));
-                        else *reinterpret_cast<M2M_AS1 u32x4_t*>(p_h + off) = sa;
+                        __builtin_nontemporal_store(sa, reinterpret_cast<M2M_AS1 u32x4_t*>(p_h + off));
                     }
                 } else {
                     // fp32: a 16-row half is a whole k-block: [column tile][32-row pair][half][lane][16 bytes]
@@ -882,13 +807,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
                     }
                 }
             }
-#endif   // M2M_ABL_NOTR
             TIMER_CMARK(12);   // transposing MFMAs, packs, operand stores
-#ifdef M2M_ABL_NOP3
-            asm volatile("" :: "v"(hf[0][0].u));
-            q = qn;
-            continue;
-#endif
             if constexpr (W1LDS) {
                 typedef short s16x4 __attribute__((ext_vector_type(4)));
                 typedef __attribute__((address_space(3))) s16x4* lds_s16x4_p;
@@ -916,7 +835,6 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
             TIMER_CMARK(13);   // third product (transposed reads of the parked W1 + MFMAs)
             q = qn;
         }
-        if (TICKETS && M2M_PRIO_STATIC) __builtin_amdgcn_s_setprio(0);
         TIMER_CMARK(14);   // (loop exit)
         TIMER_LMARK(2);   // C3 hidden-column loop (wave 0)
         int tb2 = tid;
@@ -1028,7 +946,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
                 for (int w = 0; w < NWAVES; ++w) v += red[w * TokRed<NM>::LD + slot];
                 float* sl = slot_of(b);
                 if constexpr (PART) sl[SPP_TOK(D) + i] = v;
-                else M2M_SMALL_ATOMIC(dst, v);
+                else atomicAdd(dst, v);
             }
         } else {
             { float* sl = slot_of(b); if constexpr (PART) colsums(t_prod, t_up, sl + SPP_LN2, sl + SPP_LN2 + D, tb3, true); else colsums(t_prod, t_up, bk.g_ln2_w, bk.g_ln2_b, tb3); }
@@ -1088,7 +1006,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
                             dh = __builtin_fmaf(w2r[n][tt], dv[n], dh);
                         }
                         float gl, dgl;                                   // both carry the dropout scale
-                        ActB<P>::gelu_grad_scaled(gtab, h, dr_th.scale, gl, dgl);
+                        Act<P>::gelu_grad_scaled(gtab, h, dr_th.scale, gl, dgl);
                         const bool keep = (wth >> (t & 31)) & 1u;
                         const float hact = keep ? gl : 0.f;
                         const float dhp = (keep && pv) ? dh * dgl : 0.f;
@@ -1152,7 +1070,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
                 for (int w = 0; w < NWAVES; ++w) v += red[w * RED_LD + slot];
                 float* sl = slot_of(b);
                 if constexpr (PART) sl[SPP_TOK(D) + i] = v;
-                else M2M_SMALL_ATOMIC(dst, v);
+                else atomicAdd(dst, v);
             }
         }
         // (R3) LayerNorm-1 backward on the row thread's registers: dx_in = dx_mid + LN1'(dU); the sources of the LN1 parameter
@@ -1221,7 +1139,7 @@ static __device__ __forceinline__ void tower_bwd_body(const TW& tw, int B, const
 }
 
 template <int P, int D, int NMAX, int TG, int DM, bool PART = false, bool HREC = false>
-__global__ __launch_bounds__(NTHREADS) M2M_BWD_KATTR void tower_bwd_kernel(const m2m_tower tw, int B, const float* __restrict__ d_out,
+__global__ __launch_bounds__(NTHREADS) void tower_bwd_kernel(const m2m_tower tw, int B, const float* __restrict__ d_out,
                                                              long d_out_ss, const float* __restrict__ d_pooled,
                                                              float* __restrict__ d_x0, long d_x0_ss, unsigned int seed,
                                                              unsigned int step_host, const unsigned int* __restrict__ step_dev) {
@@ -1231,7 +1149,7 @@ __global__ __launch_bounds__(NTHREADS) M2M_BWD_KATTR void tower_bwd_kernel(const
 }
 // the same with the classification heads in its prologue (BwdHeads); slot form only
 template <int P, int D, int NMAX, int TG, int DM, bool HREC>
-__global__ __launch_bounds__(NTHREADS) M2M_BWD_KATTR void tower_bwd_heads_kernel(const m2m_tower tw, const BwdHeads hd, int B, float* __restrict__ d_x0,
+__global__ __launch_bounds__(NTHREADS) void tower_bwd_heads_kernel(const m2m_tower tw, const BwdHeads hd, int B, float* __restrict__ d_x0,
                                                                    long d_x0_ss, unsigned int seed, unsigned int step_host,
                                                                    const unsigned int* __restrict__ step_dev) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1255,7 +1173,7 @@ static_assert(sizeof(BwdGroupArgs) <= 3584, "kernel arguments are limited to 4 K
 
 // Small parameter gradients (LayerNorms, token MLP, ch_b2) through per-workgroup slots + one reduction launch instead of float
 // atomics: fused-class towers whose descriptor carries the slot buffer (m2m_tower.gpart: the runtime allocates it for bf16,
-// hidden_dim 128).  Timing ablation without these atomics (M2M_ABL_NOATOM): fusion backward -9 us, two-tower backward -7 us --
+// hidden_dim 128).  Timing ablation without these atomics: fusion backward -9 us, two-tower backward -7 us --
 // 256 (128) workgroups add to the same ~3000 addresses.  With slots the single-tower launch (the fusion tower: 256-way
 // contention) nets -3 us including its reduction launch, and its small gradients no longer depend on the order of the atomics.
 // M2M_SMALL_PART=0 keeps the atomics everywhere.
@@ -1290,7 +1208,7 @@ bool m2m_small_part_deferred(SplitReduceTower& x, const m2m_tower* t, int B) {
     return true;
 }
 template <int P, int D, int NMAX, int TG, int DM, bool PART = false, bool HREC = false>
-__global__ __launch_bounds__(NTHREADS) M2M_BWD_KATTR void tower_bwd_group_kernel(const BwdGroupArgs a, int B, unsigned int seed,
+__global__ __launch_bounds__(NTHREADS) void tower_bwd_group_kernel(const BwdGroupArgs a, int B, unsigned int seed,
                                                                    unsigned int step_host, const unsigned int* __restrict__ step_dev) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     // XCD-aware mapping: workgroups are dealt to the 8 XCDs round-robin (id % 8), each XCD has its own 4 MB L2.  Tower 0

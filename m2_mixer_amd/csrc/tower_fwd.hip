@@ -37,9 +37,6 @@ template <int P, int D, int NMAX> struct FwdLds {
 #define M2M_LDS_MAX 163840
 #endif
 
-#ifndef M2M_FWD_TICKETS
-#define M2M_FWD_TICKETS 0     // measured: -0.6 % step time, at the price of run-to-run different forward sums (off)
-#endif
 TIMER_DECL(g_tm_fwd);
 TIMER_READER(m2m_debug_timers_fwd, g_tm_fwd)
 
@@ -72,7 +69,7 @@ static __device__ __forceinline__ void tower_fwd_body(const TW& tw, const float*
     unsigned int* wto = wth + SPW_ * D;                           //   (bf16 mode with dropout only: token_mfma.h)
     float* par = reinterpret_cast<float*>(wto + SPW_ * D);        // [nblocks][L::PB]
     float* bias_s = par + tw.nblocks * L::PB;                     // [Cp] hidden bias (padded layout) of the block in flight
-    unsigned int* qctr = reinterpret_cast<unsigned int*>(bias_s + tw.Cp);      // ticket counter of the column loop
+    unsigned int* qctr = reinterpret_cast<unsigned int*>(bias_s + tw.Cp);      // (leftover of the retired ticket loop: DESIGN.md, "Retired compile-time experiments")
     constexpr int PB = L::PB, O_LN1W = 0, O_LN1B = D, O_LN2W = 2 * D, O_LN2B = 3 * D, O_CHB2 = 4 * D, O_TOKW = 5 * D,
                   O_TOKB2 = 5 * D + 32 * TW_LD;
 
@@ -213,7 +210,7 @@ static __device__ __forceinline__ void tower_fwd_body(const TW& tw, const float*
         const Drop dr_ch = make_drop(training, tw.p_drop, seed, step, site + 2);
         const Drop dr_co = make_drop(training, tw.p_drop, seed, step, site + 3);
         TIMER_LMARK(0);   // block input: save / LN1 (in the previous block's last phase from block 1 on)
-        if (tid == 0) *qctr = NWAVES;      // tickets of the column loop (barriers lie between here and the loop)
+        if (tid == 0) *qctr = NWAVES;      // (nothing reads it: leftover, see above)
 
         if constexpr (TOK) {
         // ---- token mixing (modules/mixer.py:30-35): bf16 mode on the matrix pipe (token_mfma.h), fp32 mode one thread
@@ -289,17 +286,8 @@ static __device__ __forceinline__ void tower_fwd_body(const TW& tw, const float*
 #pragma unroll
                 for (int kb = 0; kb < KD; ++kb) w1f[t][kb] = ld_frag_global(bk.w1n, (long)(2 * wave + t) * KD + kb, lane);
         }
-        // bf16 training: steps by ticket, as in tower_bwd.hip (inference and the fp32 parity mode keep the static split:
-        // reproducible sums)
-        const bool tickets = P == PREC_BF16 && M2M_FWD_TICKETS && training;
-        // stagger of the younger half (waves 4-7 share their SIMDs with waves 0-3): see tower_bwd.hip
-#ifndef M2M_FWD_STAGGER
-#define M2M_FWD_STAGGER 0
-#endif
-        if (M2M_FWD_STAGGER > 0 && P == PREC_BF16 && __builtin_amdgcn_readfirstlane(wave) >= NWAVES / 2) __builtin_amdgcn_s_sleep(M2M_FWD_STAGGER);
+        // static split of the steps over the waves: reproducible sums (by ticket, staggered: DESIGN.md, "Retired compile-time experiments")
         for (int q = __builtin_amdgcn_readfirstlane(wave); q < npairs;) {
-            unsigned int ticket = 0u;
-            if (tickets && lane == 0) ticket = atomicAdd(qctr, 1u);
             // this step's W2 fragments: in flight during GEMM1 + epilogue
             Frag w2f[NF][DT];
 #pragma unroll
@@ -328,7 +316,7 @@ static __device__ __forceinline__ void tower_fwd_body(const TW& tw, const float*
             // prefetch the next step's W1 fragments under the epilogue (scheduling barrier: do not hoist the
             // loads above the MFMAs that still read the current fragments)
             __builtin_amdgcn_sched_barrier(0);
-            const int qn = tickets ? (int)__builtin_amdgcn_readfirstlane(ticket) : q + NWAVES;
+            const int qn = q + NWAVES;
             if (qn < npairs) {
 #pragma unroll
                 for (int t = 0; t < 2; ++t)
@@ -338,10 +326,7 @@ static __device__ __forceinline__ void tower_fwd_body(const TW& tw, const float*
             }
             // bias is already in; GELU + dropout on the accumulators (row c = 32q + 16t + 4g + r, column m = il)
             Frag hf[MT][NF];
-#ifndef M2M_FWD_STAGED
-#define M2M_FWD_STAGED 1
-#endif
-            if constexpr (M2M_FWD_STAGED && Act<P>::USES_TABLE && MT == 1) {
+            if constexpr (Act<P>::USES_TABLE && MT == 1) {
                 // the eight table look-ups as one batch (indices, then all reads in flight, then the fmas): left to itself the
                 // compiler issues them 1 + 3 + 1 + 3 with a full LDS wait after each group
                 const unsigned int m = (unsigned int)(row0 + il);

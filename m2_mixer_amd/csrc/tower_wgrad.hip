@@ -26,19 +26,12 @@
 #endif
 
 #define WBM 32            // rows per streamed tile (= two 16-row tiles of the chain kernels when BM == 16)
-#ifndef WG_RING_MAX
 #define WG_RING_MAX 24    // VGPR budget of one tile in flight that still allows a second one (register ring depth 2)
-#endif
 #define WG_WAVES 4        // waves of a tower workgroup, except:
-#ifndef WG_WAVES_WIDE
 #define WG_WAVES_WIDE 5   // bf16, hidden_dim 128 (the stored-operand form of M2-Mixer-B): 160 hidden columns per workgroup -> 240
-#endif                    // workgroups for the model, ONE per CU, all of the same length (towers alone: 102 -> 80 us)
-#ifndef WG_LA
+                          // workgroups for the model, ONE per CU, all of the same length (towers alone: 102 -> 80 us)
 #define WG_LA 4           // LDS fragments read ahead of their MFMAs
-#endif
-#ifndef WG_MINWAVES
 #define WG_MINWAVES 2
-#endif
 #define WG_OUT_ATOMIC 0   // how a workgroup hands over its results (wgrad_write_w)
 #define WG_OUT_ADD 1
 #define WG_OUT_STORE 2    // "=": single owner, the old values are not read (m2m_tower.wgrad_flags & M2M_WGRAD_OVERWRITE, and the
@@ -49,54 +42,26 @@ TIMER_READER(m2m_debug_timers_wgrad, g_tm_wg)
 
 #include "tower_wgrad_rc.h"   // WgOut, wgrad_write_w, the recompute form (bf16, hidden_dim 128)
 
-// Round 4 experiment, bf16 / hidden_dim 128 (-DM2M_WG48=1; OFF): FOUR waves x THREE 16-column tiles = 192 hidden columns per
-// workgroup, one wave per SIMD with up to 512 registers and a deeper register ring.  Idea: the five-wave form puts two waves on
-// SIMD 0 (2 x 36 MFMAs per 32-row step = 0.55 us against 0.28 us on the other SIMDs); here every SIMD issues 54 MFMAs per step
-// and the 196 workgroups of M2-Mixer-B leave 60 CUs to the embedding workgroups.  MEASURED (parity-green, two interleaved
-// repetitions in one process): merged launch 132-134 us (embedding workgroups first) / 116 us (last) against 105 us for the
-// five-wave form, ring depth 1 or 2 alike -- the step is not paced by SIMD 0's MFMAs but by the latency chain stage write ->
-// barrier -> LDS fragment reads -> MFMAs, which a lone wave per SIMD hides worse than five waves on four SIMDs do; the L2's
-// memory-side queue shows ~1200 cycles per read for this launch (profiles/r04_ea_read_latency.txt: HBM, not Infinity Cache).
-#ifndef M2M_WG48
-#define M2M_WG48 0
-#endif
-#ifndef WG48_DEPTH
-#define WG48_DEPTH 2
-#endif
+// (Retired tilings -- four waves x three column tiles, several token tiles per step, every stream on LDS-DMA: DESIGN.md,
+// "Retired compile-time experiments".)
 template <int P, int D> struct WgradGeom {
     static constexpr int NF = Chain<P>::NF;
-    static constexpr bool W48 = M2M_WG48 && P == PREC_BF16 && D == 128;
-    static constexpr int WAVES = W48 ? 4 : ((P == PREC_BF16 && D == 128) ? WG_WAVES_WIDE : WG_WAVES);
+    static constexpr int WAVES = (P == PREC_BF16 && D == 128) ? WG_WAVES_WIDE : WG_WAVES;
     static constexpr int THREADS = WAVES * 64;
-#ifdef WG_CPW_FORCE
-    static constexpr int CPW = WG_CPW_FORCE;
-#else
-    static constexpr int CPW = W48 ? 3 : ((P == PREC_BF16 && D <= 128) ? 2 : 1);     // 16-column tiles per wave
-#endif
+    static constexpr int CPW = (P == PREC_BF16 && D <= 128) ? 2 : 1;                  // 16-column tiles per wave
     static constexpr int IMG_B = WBM * D * Prec<P>::ESZ;
     static constexpr int STAGE_B = 2 * IMG_B;                                          // A^T | dYd^T of one tile
     static constexpr int NLD = (STAGE_B + THREADS * 16 - 1) / (THREADS * 16);   // 16-byte pieces per thread per tile
-    // token tiles per step (= per barrier).  Measured on M2-Mixer-B: 4 tiles per step with one workgroup per CU (the next
-    // step's 128 KiB of loads in flight in up to 512 VGPRs) was SLOWER (230 vs 160 us for the three towers) than one
-    // tile per step with two workgroups per CU, so 1 is the default; the knob stays for other shapes.
-#ifdef WG_TPS_FORCE
-    static constexpr int TPS = (P == PREC_BF16 && D <= 128) ? WG_TPS_FORCE : 1;
-#else
-    static constexpr int TPS = 1;
-#endif
+    // One token tile per step (= per barrier), two workgroups per CU.
     static constexpr int RING_REGS = NLD * 4 + CPW * 2 * NF * 4;                      // VGPRs of one tile in flight
-    static constexpr int DEPTH = W48 ? WG48_DEPTH : ((TPS == 1 && RING_REGS <= WG_RING_MAX) ? 2 : 1);      // steps of loads in flight
+    static constexpr int DEPTH = RING_REGS <= WG_RING_MAX ? 2 : 1;                    // steps of loads in flight
     static constexpr int COLS = WAVES * CPW * 16;                                   // hidden columns per workgroup
     static constexpr int TR_B = WAVES * 16 * (D + 4) * 4;                          // dW1 write-out transpose: 16 x (D + 4) floats per wave
-    static constexpr int LDS_B = 2 * TPS * STAGE_B > TR_B ? 2 * TPS * STAGE_B : TR_B;  // dynamic LDS of the kernel
-    static constexpr int MINWAVES = (W48 || TPS > 2) ? 1 : 2;                          // waves per SIMD the kernel is built for
+    static constexpr int LDS_B = 2 * STAGE_B > TR_B ? 2 * STAGE_B : TR_B;              // dynamic LDS of the kernel
+    static constexpr int MINWAVES = WG_MINWAVES;                                       // waves per SIMD the kernel is built for
     // the wave's own Hact^T / dHpre^T fragments (the HBM stream: read once, ~1200 cycles per read under load) requested TWO
     // steps ahead, the shared stage (L2-resident images) one step ahead: 16 registers more than a ring of one step
-#ifndef M2M_WG_HD2
-#define M2M_WG_HD2 1
-#endif
-    static constexpr bool HD2 = M2M_WG_HD2 && !W48 && P == PREC_BF16 && D == 128 && TPS == 1 && DEPTH == 1;
-    static_assert(TPS == 1 || DEPTH == 1, "multi-tile steps use a ring of one step");
+    static constexpr bool HD2 = P == PREC_BF16 && D == 128 && DEPTH == 1;
 };
 
 // One workgroup's share: column slice `slice` of block `bk`, token tiles [group * tiles_per_group, ...).
@@ -105,8 +70,7 @@ static __device__ __forceinline__ void wgrad_body(const m2m_block& bk, const WgO
                                                   int ntiles, int tiles_per_group, char* smem) {
     typedef Prec<P> Pr;
     typedef WgradGeom<P, D> G;
-    constexpr int DT = D / 16, NF = G::NF, CPW = G::CPW, IMG_B = G::IMG_B, STAGE_B = G::STAGE_B, NLD = G::NLD, DEPTH = G::DEPTH,
-                  TPS = G::TPS;
+    constexpr int DT = D / 16, NF = G::NF, CPW = G::CPW, IMG_B = G::IMG_B, STAGE_B = G::STAGE_B, NLD = G::NLD, DEPTH = G::DEPTH;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, g = lane >> 4, il = lane & 15;
     const int nct = Cp >> 4;
@@ -134,8 +98,8 @@ static __device__ __forceinline__ void wgrad_body(const m2m_block& bk, const WgO
     const gptr_t src_at = (gptr_t)bk.at_chn, src_dyt = (gptr_t)bk.dyt_chn, src_h = (gptr_t)bk.h_chn, src_dh = (gptr_t)bk.dh_chn;
     // One tile's worth of loads in flight: this thread's pieces of the shared stage + this wave's own fragments.
     struct Pre {
-        u32x4_t st[TPS][NLD];
-        Frag h[TPS][CPW][NF], d[TPS][CPW][NF];
+        u32x4_t st[NLD];
+        Frag h[CPW][NF], d[CPW][NF];
     };
     // Every load below is unconditional (indices clamped into range, a few redundant loads at the tail): with a fixed
     // number of loads per step the compiler can place counted s_waitcnt vmcnt(N) and really keep DEPTH tiles in flight;
@@ -144,6 +108,10 @@ static __device__ __forceinline__ void wgrad_body(const m2m_block& bk, const WgO
     int ctl[CPW];                                           // column tiles past the end (last slice) shadow the last one
 #pragma unroll
     for (int j = 0; j < CPW; ++j) ctl[j] = min(ct0 + j, nct - 1);
+    // (The one-trip loop is what is left of the several-tiles-per-step experiment.  Without it the generic instantiations come
+    //  out with the same instructions but other register numbers, so it stays until a change that is measured: DESIGN.md,
+    //  "Retired compile-time experiments".)
+    constexpr int TPS = 1;
     auto tile_load = [&](Pre& p, int tile0, int t_end) {
 #pragma unroll
         for (int u = 0; u < TPS; ++u) {
@@ -152,51 +120,29 @@ static __device__ __forceinline__ void wgrad_body(const m2m_block& bk, const WgO
             for (int i = 0; i < NLD; ++i) {
                 const int o = min((i * G::THREADS + tid) * 16, STAGE_B - 16);
                 const gptr_t sp = o < IMG_B ? src_at : src_dyt;
-                p.st[u][i] = *(const M2M_GLOBAL_AS u32x4_t*)(sp + (long)tile * IMG_B + (o < IMG_B ? o : o - IMG_B));
+                p.st[i] = *(const M2M_GLOBAL_AS u32x4_t*)(sp + (long)tile * IMG_B + (o < IMG_B ? o : o - IMG_B));
             }
             if (P == PREC_BF16) {
                 // [column-tile pair][32-row pair][16-row half][lane][tile 2q: 8 B | tile 2q+1: 8 B]  (written by tower_bwd.hip)
                 // read exactly once: non-temporal, so the stream does not evict the A^T / dYd^T tiles that the other column
                 // slices of this block re-read from L2
                 const long blk = (long)(ctl[0] >> 1) * m2m_hchn_stride(ntiles) + (long)tile * 2048 + lane * 16;
-                if (CPW == 3) {
-                    // three tiles = a whole column-tile pair + one half of the neighbouring pair (wave-uniform: which half, and on
-                    // which side, follows from the parity of the wave's first tile): 16-byte loads for the pair, 8-byte loads for
-                    // the half slot (the other 8 bytes of those slots go to the neighbouring wave of this workgroup)
-                    typedef const M2M_GLOBAL_AS u32x4_t* g4_t;
-                    typedef const M2M_GLOBAL_AS u32x2_t* g2_t;
-                    const bool odd = (__builtin_amdgcn_readfirstlane(ct0) & 1) != 0;
-                    const int plast = (nct >> 1) - 1;
-                    const int pfull = min(odd ? (ct0 + 1) >> 1 : ct0 >> 1, plast), phalf = min(odd ? ct0 >> 1 : (ct0 + 2) >> 1, plast);
-                    const long strd = m2m_hchn_stride(ntiles);
-                    const long bf = (long)pfull * strd + (long)tile * 2048 + lane * 16;
-                    const long bh = (long)phalf * strd + (long)tile * 2048 + lane * 16 + (odd ? 8 : 0);
-                    const u32x4_t h0 = __builtin_nontemporal_load((g4_t)(src_h + bf)), h1 = __builtin_nontemporal_load((g4_t)(src_h + bf + 1024));
-                    const u32x4_t d0 = __builtin_nontemporal_load((g4_t)(src_dh + bf)), d1 = __builtin_nontemporal_load((g4_t)(src_dh + bf + 1024));
-                    const u32x2_t hh0 = __builtin_nontemporal_load((g2_t)(src_h + bh)), hh1 = __builtin_nontemporal_load((g2_t)(src_h + bh + 1024));
-                    const u32x2_t dd0 = __builtin_nontemporal_load((g2_t)(src_dh + bh)), dd1 = __builtin_nontemporal_load((g2_t)(src_dh + bh + 1024));
-                    const u32x4_t hf0 = u32x4_t{h0[0], h0[1], h1[0], h1[1]}, hf1 = u32x4_t{h0[2], h0[3], h1[2], h1[3]};
-                    const u32x4_t df0 = u32x4_t{d0[0], d0[1], d1[0], d1[1]}, df1 = u32x4_t{d0[2], d0[3], d1[2], d1[3]};
-                    const u32x4_t hhf = u32x4_t{hh0[0], hh0[1], hh1[0], hh1[1]}, dhf = u32x4_t{dd0[0], dd0[1], dd1[0], dd1[1]};
-                    p.h[u][0][0].u = odd ? hhf : hf0;  p.d[u][0][0].u = odd ? dhf : df0;
-                    p.h[u][1 % CPW][0].u = odd ? hf0 : hf1;  p.d[u][1 % CPW][0].u = odd ? df0 : df1;
-                    p.h[u][2 % CPW][0].u = odd ? hf1 : hhf;  p.d[u][2 % CPW][0].u = odd ? df1 : dhf;
-                } else if (CPW == 2) {                       // the wave owns both tiles of the pair: one 16-byte load per half
+                if (CPW == 2) {                       // the wave owns both tiles of the pair: one 16-byte load per half
                     typedef const M2M_GLOBAL_AS u32x4_t* g4_t;
                     const u32x4_t h0 = __builtin_nontemporal_load((g4_t)(src_h + blk)), h1 = __builtin_nontemporal_load((g4_t)(src_h + blk + 1024));
                     const u32x4_t d0 = __builtin_nontemporal_load((g4_t)(src_dh + blk)), d1 = __builtin_nontemporal_load((g4_t)(src_dh + blk + 1024));
 #pragma unroll
                     for (int j = 0; j < CPW; ++j) {
-                        p.h[u][j][0].u = u32x4_t{h0[2 * j], h0[2 * j + 1], h1[2 * j], h1[2 * j + 1]};
-                        p.d[u][j][0].u = u32x4_t{d0[2 * j], d0[2 * j + 1], d1[2 * j], d1[2 * j + 1]};
+                        p.h[j][0].u = u32x4_t{h0[2 * j], h0[2 * j + 1], h1[2 * j], h1[2 * j + 1]};
+                        p.d[j][0].u = u32x4_t{d0[2 * j], d0[2 * j + 1], d1[2 * j], d1[2 * j + 1]};
                     }
                 } else {                                     // one tile of the pair: its 8-byte half of every lane slot
                     typedef const M2M_GLOBAL_AS u32x2_t* g2_t;
                     const long o = blk + (ctl[0] & 1) * 8;
                     const u32x2_t h0 = __builtin_nontemporal_load((g2_t)(src_h + o)), h1 = __builtin_nontemporal_load((g2_t)(src_h + o + 1024));
                     const u32x2_t d0 = __builtin_nontemporal_load((g2_t)(src_dh + o)), d1 = __builtin_nontemporal_load((g2_t)(src_dh + o + 1024));
-                    p.h[u][0][0].u = u32x4_t{h0[0], h0[1], h1[0], h1[1]};
-                    p.d[u][0][0].u = u32x4_t{d0[0], d0[1], d1[0], d1[1]};
+                    p.h[0][0].u = u32x4_t{h0[0], h0[1], h1[0], h1[1]};
+                    p.d[0][0].u = u32x4_t{d0[0], d0[1], d1[0], d1[1]};
                 }
             } else {
                 typedef const M2M_GLOBAL_AS u32x4_t* g4_t;
@@ -205,71 +151,60 @@ static __device__ __forceinline__ void wgrad_body(const m2m_block& bk, const WgO
 #pragma unroll
                     for (int f = 0; f < NF; ++f) {           // fp32: [column tile][32-row pair][half = k-block f][lane][16 B]
                         const long blk = (long)ctl[j] * m2m_hchn_stride(ntiles) + ((long)tile * NF + f) * 1024 + lane * 16;
-                        p.h[u][j][f].u = __builtin_nontemporal_load((g4_t)(src_h + blk));
-                        p.d[u][j][f].u = __builtin_nontemporal_load((g4_t)(src_dh + blk));
+                        p.h[j][f].u = __builtin_nontemporal_load((g4_t)(src_h + blk));
+                        p.d[j][f].u = __builtin_nontemporal_load((g4_t)(src_dh + blk));
                     }
                 }
             }
         }
     };
-    // Consume the step (TPS tiles from `tile0`) held in p, then refill p with the step DEPTH ahead.  One barrier per step:
+    // Consume the tile held in p, then refill p with the tile DEPTH ahead.  One barrier per step:
     // the stage written in step i (buffer i & 1) was last read in step i - 2, and every wave has passed the barrier of
     // step i - 1 since.
-    auto step = [&](Pre& p, int tile0, int t_end, int i) {
-        char* buf = smem + (i & 1) * (TPS * STAGE_B);
+    auto step = [&](Pre& p, int tile, int t_end, int i) {
+        char* cur = smem + (i & 1) * STAGE_B;
 #pragma unroll
-        for (int u = 0; u < TPS; ++u) {
-            char* cur = buf + u * STAGE_B;
-#pragma unroll
-            for (int k = 0; k < NLD; ++k) {
-                const int o = (k * G::THREADS + tid) * 16;
-                if (o < STAGE_B) *reinterpret_cast<u32x4_t*>(cur + o) = p.st[u][k];
-            }
+        for (int k = 0; k < NLD; ++k) {
+            const int o = (k * G::THREADS + tid) * 16;
+            if (o < STAGE_B) *reinterpret_cast<u32x4_t*>(cur + o) = p.st[k];
         }
-        Frag hf[TPS][CPW][NF], df[TPS][CPW][NF];
+        Frag hf[CPW][NF], df[CPW][NF];
 #pragma unroll
-        for (int u = 0; u < TPS; ++u)
+        for (int j = 0; j < CPW; ++j)
 #pragma unroll
-            for (int j = 0; j < CPW; ++j)
-#pragma unroll
-                for (int f = 0; f < NF; ++f) { hf[u][j][f] = p.h[u][j][f]; df[u][j][f] = p.d[u][j][f]; }
+            for (int f = 0; f < NF; ++f) { hf[j][f] = p.h[j][f]; df[j][f] = p.d[j][f]; }
         TIMER_MARK(g_tm_wg, 0);    // wait for this step's loads + stage write
-        tile_load(p, min(tile0 + DEPTH * TPS, t_end - 1), t_end);
+        tile_load(p, min(tile + DEPTH, t_end - 1), t_end);
         TIMER_MARK(g_tm_wg, 1);    // issue of the refill loads
         __syncthreads();
         TIMER_MARK(g_tm_wg, 2);    // barrier
+        // The shared operands come from LDS one 1-KiB fragment per (f, dt); with one wave per SIMD nothing else hides
+        // the ds_read latency, so the reads run WG_LA fragments ahead of the MFMAs that consume them (measured: the
+        // compiler's own distance of one made the loop LDS-latency-bound at 0.83 us per tile).
+        constexpr int NQ = NF * DT;
+        constexpr int LA = WG_LA < NQ ? WG_LA : NQ;
+        Frag aq[LA], dq[LA];
 #pragma unroll
-        for (int u = 0; u < TPS; ++u) {
-            if (TPS > 1 && tile0 + u >= t_end) break;
-            const char* cur = buf + u * STAGE_B;
-            // The shared operands come from LDS one 1-KiB fragment per (f, dt); with one wave per SIMD nothing else hides
-            // the ds_read latency, so the reads run WG_LA fragments ahead of the MFMAs that consume them (measured: the
-            // compiler's own distance of one made the loop LDS-latency-bound at 0.83 us per tile).
-            constexpr int NQ = NF * DT;
-            constexpr int LA = WG_LA < NQ ? WG_LA : NQ;
-            Frag aq[LA], dq[LA];
+        for (int q = 0; q < LA; ++q) {
+            aq[q] = ld_frag_lds(cur, q, lane);
+            dq[q] = ld_frag_lds(cur + IMG_B, q, lane);
+        }
 #pragma unroll
-            for (int q = 0; q < LA; ++q) {
-                aq[q] = ld_frag_lds(cur, q, lane);
-                dq[q] = ld_frag_lds(cur + IMG_B, q, lane);
+        for (int q = 0; q < NQ; ++q) {
+            const int f = q / DT, dt = q % DT;
+            const Frag at = aq[q % LA], dyt = dq[q % LA];
+            if (q + LA < NQ) {
+                aq[q % LA] = ld_frag_lds(cur, q + LA, lane);
+                dq[q % LA] = ld_frag_lds(cur + IMG_B, q + LA, lane);
             }
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) {
-                const int f = q / DT, dt = q % DT;
-                const Frag at = aq[q % LA], dyt = dq[q % LA];
-                if (q + LA < NQ) {
-                    aq[q % LA] = ld_frag_lds(cur, q + LA, lane);
-                    dq[q % LA] = ld_frag_lds(cur + IMG_B, q + LA, lane);
-                }
+            for (int j = 0; j < CPW; ++j) {
+                Pr::mma(dw1[j][dt], df[j][f], at);
+                Pr::mma(dw2[j][dt], hf[j][f], dyt);
+            }
+            if (dt == DT - 1) {
 #pragma unroll
-                for (int j = 0; j < CPW; ++j) {
-                    Pr::mma(dw1[j][dt], df[u][j][f], at);
-                    Pr::mma(dw2[j][dt], hf[u][j][f], dyt);
-                }
-                if (dt == DT - 1) {
-#pragma unroll
-                    for (int j = 0; j < CPW; ++j) Pr::mma(db1[j], df[u][j][f], ones);   // every column = sum over the tile's rows of dHpre[.][c]
-                }
+                for (int j = 0; j < CPW; ++j) Pr::mma(db1[j], df[j][f], ones);   // every column = sum over the tile's rows of dHpre[.][c]
             }
         }
         TIMER_MARK(g_tm_wg, 3);    // LDS reads + MFMAs
@@ -349,10 +284,10 @@ static __device__ __forceinline__ void wgrad_body(const m2m_block& bk, const WgO
     } else {
     Pre p[DEPTH];
 #pragma unroll
-    for (int k = 0; k < DEPTH; ++k) tile_load(p[k], min(t_begin + k * TPS, t_end - 1), t_end);
+    for (int k = 0; k < DEPTH; ++k) tile_load(p[k], min(t_begin + k, t_end - 1), t_end);
     int tile = t_begin, it = 0;
     if (DEPTH == 1) {
-        for (; tile < t_end; tile += TPS) step(p[0], tile, t_end, it++);
+        for (; tile < t_end; ++tile) step(p[0], tile, t_end, it++);
     } else {
         for (; tile + DEPTH <= t_end; tile += DEPTH) {       // full trips: straight-line, fixed load count
 #pragma unroll
@@ -407,24 +342,10 @@ static __device__ __forceinline__ WgOut wgrad_out(const TW& tw, int b, int group
     return o;
 }
 
-// the stored-operand form with every stream on LDS-DMA (tower_wgrad_rc.h: wgrad_dma_body) exists for these instantiations
-// Compile-time choice (both loops in one kernel spilled 60 registers); OFF by default (-DM2M_WGRAD_DMA=1 builds it).  Measured on
-// M2-Mixer-B, batch 512, A/B in one process: merged launch 108.3 / 107.2 us with the DMA loop against 107.3 / 106.3 us with the
-// register-staged one; the three towers alone 90 against 82 us.  Three steps of prefetch instead of one change nothing: the loop is
-// not waiting for its operand streams any more (in-kernel timers, scripts/rc_timers.py: per 32-row step 0.46 us LDS reads + MFMAs,
-// 0.24 us DMA issue -- 8 pieces per wave at ~75 cycles each --, 0.18 us barrier, 0.14 us DMA wait; write-out 13 us), and with five
-// waves per workgroup SIMD 0 carries two of them: 2 x 36 MFMAs x 16 cycles = 0.55 us per step is the floor of this tiling.
-#ifndef M2M_WGRAD_DMA
-#define M2M_WGRAD_DMA 0
-#endif
-template <int P, int D, int RCDM> struct WgradHasDma { static constexpr bool value = M2M_WGRAD_DMA && RCDM < 0 && P == PREC_BF16 && D == 128; };
-
 // RCDM: -1 = stored-operand form; DM_NONE / DM_HALF = recompute form with that dropout mode (bf16, hidden_dim 128 only)
 template <int P, int D, int RCDM> struct WgradKernelGeom {
     static constexpr bool RC = RCDM >= 0;
-    static constexpr int LDS_PLAIN = RC ? RcGeom<D>::LDS_B : WgradGeom<P, D>::LDS_B;
-    static constexpr int LDS_DMA = DrGeom<D, WgradGeom<P, D>::WAVES>::LDS_B;
-    static constexpr int LDS_B = WgradHasDma<P, D, RCDM>::value ? LDS_DMA : LDS_PLAIN;
+    static constexpr int LDS_B = RC ? RcGeom<D>::LDS_B : WgradGeom<P, D>::LDS_B;
     static constexpr int COLS = RC ? RcGeom<D>::COLS : WgradGeom<P, D>::COLS;
     static constexpr int MINWAVES = RC ? 2 : WgradGeom<P, D>::MINWAVES;
     static constexpr int THREADS = RC ? RC_THREADS : WgradGeom<P, D>::THREADS;
@@ -432,27 +353,24 @@ template <int P, int D, int RCDM> struct WgradKernelGeom {
 
 template <int P, int D, int RCDM, class TW>
 static __device__ __forceinline__ void wgrad_dispatch(const TW& tw, int b, int slice, int group, int ngroups, int slot_mode, int ntiles,
-                                                      int tpg, int rows_per_t16, unsigned int seed, unsigned int step, int dma, char* smem) {
+                                                      int tpg, int rows_per_t16, unsigned int seed, unsigned int step, char* smem) {
     const WgOut out = wgrad_out(tw, b, group, ngroups, slot_mode);
     if constexpr (RCDM >= 0) {
         const Drop dr = make_drop(true, tw.p_drop, seed, step, tw.site_base + 4u * (unsigned int)b + 2u);
         wgrad_rc_body<D, RCDM>(tw.blk[b], out, tw.Cp, tw.C, slice, group, ntiles, tpg, rows_per_t16, dr.key, dr.scale, smem);
     } else {
-        if constexpr (WgradHasDma<P, D, RCDM>::value)
-            wgrad_dma_body<D, WgradGeom<P, D>::WAVES>(tw.blk[b], out, tw.Cp, tw.C, slice, group, ntiles, tpg, smem);
-        else
-            wgrad_body<P, D>(tw.blk[b], out, tw.Cp, tw.C, slice, group, ntiles, tpg, smem);
+        wgrad_body<P, D>(tw.blk[b], out, tw.Cp, tw.C, slice, group, ntiles, tpg, smem);
     }
 }
 
 template <int P, int D, int RCDM>
 __global__ __launch_bounds__((WgradKernelGeom<P, D, RCDM>::THREADS), (WgradKernelGeom<P, D, RCDM>::MINWAVES)) void tower_wgrad_kernel(
     const m2m_tower tw, int ntiles, int tiles_per_group, int slot_mode, int rows_per_t16, unsigned int seed, unsigned int step_host,
-    const unsigned int* __restrict__ step_dev, int dma) {
+    const unsigned int* __restrict__ step_dev, int dma) {        // (dma: unread; kept so the argument layout is the parent's)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const unsigned int step = step_host + (step_dev ? *step_dev : 0u);
     wgrad_dispatch<P, D, RCDM>(tw, (int)blockIdx.y, (int)blockIdx.x, (int)blockIdx.z, (int)gridDim.z, slot_mode, ntiles, tiles_per_group,
-                               rows_per_t16, seed, step, dma, smem);
+                               rows_per_t16, seed, step, smem);
 }
 
 // Several towers in ONE launch (job = (tower, block)): the three towers of a model finish their backward chains at about the
@@ -468,7 +386,7 @@ struct WgradGroupArgs {
     short job_start[WG_MAX_JOBS + 1];                 // first linear workgroup index of job j (its workgroups: group-major, slice fastest)
     short xcd_start[8], xcd_len[8];                   // XCD x runs linear indices [xcd_start[x], xcd_start[x] + xcd_len[x])
     int njobs, n_tower_wgs;                           // n_tower_wgs = 8 x the longest XCD chunk (ids beyond a chunk return at once)
-    int dma;                                          // stored-operand form: every stream on LDS-DMA (wgrad_dma_body)
+    int dma;                                          // unread; kept so the argument layout is the parent's
     int n_embed_first, n_embed_pad;                   // embedding workgroups dispatched FIRST: ids [0, n_embed_first), padded to a
                                                       // multiple of 8 (n_embed_pad) so that tower ids keep their XCD (id % 8)
     int n_reduce, reduce_sets;                         // slot-reduction workgroups at the END of the grid: SPR_NBX x reduce_sets x ra.ntow
@@ -485,11 +403,8 @@ struct WgradGroupArgs {
 // Then -- dispatched last, back-filling the CUs whose tower workgroup has finished -- the workgroups of the model's two
 // patch-embedding weight gradients (embed_wgrad.h); a second launch beside this one costs a fork and a join in the replayed
 // graph (~10 us each) and slows this kernel by contending for the same CUs.
-#ifndef M2M_WG_KATTR
-#define M2M_WG_KATTR
-#endif
 template <int P, int D, int RCDM>
-__global__ __launch_bounds__((WgradKernelGeom<P, D, RCDM>::THREADS), (WgradKernelGeom<P, D, RCDM>::MINWAVES)) M2M_WG_KATTR void tower_wgrad_group_kernel(const WgradGroupArgs a,
+__global__ __launch_bounds__((WgradKernelGeom<P, D, RCDM>::THREADS), (WgradKernelGeom<P, D, RCDM>::MINWAVES)) void tower_wgrad_group_kernel(const WgradGroupArgs a,
                                                                                                           const EmbedWgradGroupArgs ea,
                                                                                                           const SplitReduceArgs ra) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -524,7 +439,7 @@ __global__ __launch_bounds__((WgradKernelGeom<P, D, RCDM>::THREADS), (WgradKerne
     const m2m_tower& tw = *a.tw[t];
     const unsigned int step = a.step_host + (a.step_dev ? *a.step_dev : 0u);
     wgrad_dispatch<P, D, RCDM>(tw, (int)a.job_block[job], slice, group, a.groups[t], a.slot[t], a.ntiles[t], a.tpg[t], a.rpt[t], a.seed,
-                               step, a.dma, smem);
+                               step, smem);
 }
 
 static_assert(sizeof(WgradGroupArgs) + sizeof(EmbedWgradGroupArgs) + sizeof(SplitReduceArgs) <= 3840, "kernel arguments are limited to 4 KiB");
@@ -573,9 +488,6 @@ static bool wgrad_slot_usable(const m2m_tower* t) {
     return true;
 }
 
-// M2M_WGRAD_DMA=0: the register-staged stored-operand loop (A/B)
-static int wgrad_use_dma() { static const int on = m2m_env_int("M2M_WGRAD_DMA", 1); return on; }
-
 struct WgradPlan { int ntiles, nsl, groups, tpg, rpt, slot; };
 // honour_overwrite == false: the plan the tower would get if its gradient were zeroed and accumulated (m2m_wgrad_groups)
 static WgradPlan wgrad_plan(const m2m_tower* t, int B, int cols, bool honour_overwrite = true) {
@@ -622,7 +534,7 @@ static int launch_wgrad(const m2m_tower* t, int B, unsigned int seed, unsigned i
     const WgradPlan pl = wgrad_plan(t, B, KG::COLS);
     const size_t lds = (size_t)KG::LDS_B;
     return m2m_launch<tower_wgrad_kernel<P, D, RCDM>>(dim3(pl.nsl, t->nblocks, pl.groups), dim3(KG::THREADS), lds, lds, st, *t, pl.ntiles, pl.tpg, 0,
-                                                      pl.rpt, seed, step, step_dev, wgrad_use_dma());
+                                                      pl.rpt, seed, step, step_dev, 0);
 }
 
 // Plans of a multi-tower launch: per tower as above; then, for a tower with a usable partial-gradient slot (m2m_tower.wslot),
@@ -689,7 +601,7 @@ static int launch_wgrad_group(const m2m_tower* const* host, const m2m_tower* con
     a.njobs = njobs; a.n_tower_wgs = 8 * max_len;
     a.seed = seed; a.step_host = step; a.step_dev = step_dev;
     a.bump_counter = bump_counter;
-    a.dma = wgrad_use_dma();
+    a.dma = 0;
     EmbedWgradGroupArgs ea;
     memset(&ea, 0, sizeof(ea));
     // The patch-embedding gradients ride in the same launch, dispatched last.  Fast form (single owner, bf16, needs the d_x0^T
