@@ -562,8 +562,12 @@ int m2m_chain_forward_rows(const m2m_tower* t, const float* x0, long x0_ss, int 
 template <int P, int D, int NMAX, int DM>
 static int launch_fwd_group_dm(const FwdGroupArgs& a, int B, int training, unsigned int seed, unsigned int step,
                                const unsigned int* step_dev, hipStream_t st) {
-    const size_t lds = std::max(fwd_lds_bytes<P, D, NMAX>(a.tw[0].nblocks, a.tw[0].N, a.tw[0].Cp),
-                                fwd_lds_bytes<P, D, NMAX>(a.tw[1].nblocks, a.tw[1].N, a.tw[1].Cp));
+    size_t lds = std::max(fwd_lds_bytes<P, D, NMAX>(a.tw[0].nblocks, a.tw[0].N, a.tw[0].Cp),
+                          fwd_lds_bytes<P, D, NMAX>(a.tw[1].nblocks, a.tw[1].N, a.tw[1].Cp));
+    // an embedding prologue runs embed_fwd_body<P, D, BM> in the same LDS first: its layout (embed.hip: launch_embed_fwd) is
+    // LARGER than a small tower's (fp32, hidden_dim 32, one block, Cp 32: 32592 / 33104 bytes against 33152)
+    if (a.embed[0] || a.embed[1])
+        lds = std::max(lds, (size_t)BM * EMB_LD * 4 + (size_t)BM * EMB_KS * Prec<P>::ESZ + EMB_KMAX * 4 + BM * 8);
     if (lds > M2M_LDS_MAX || a.tw[0].Cp > 8 * NTHREADS || a.tw[1].Cp > 8 * NTHREADS) {
         m2m_set_error("towers_forward: blocks x channel_dim exceed the workgroup's LDS", __FILE__, __LINE__);
         return -1;
