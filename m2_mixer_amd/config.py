@@ -15,6 +15,45 @@ _state = {
 }
 
 
+# ---- environment switches ---------------------------------------------------------------------------------------------------
+# Every M2M_* variable the Python package reads: name -> (default, when it is read, meaning).  Diagnostics: the defaults are the
+# measured optimum.  A default of "1" is a default-on switch (off only for "0"), "0" a default-off one (on only for "1"); None:
+# the default depends on the model (see the meaning).  INTEGRATION.md lists them beside the library's own switches
+# (tests/test_host_switches.py keeps that list complete).
+SWITCHES = {
+    "M2M_PRECISION": ("bf16", "import of config", "bf16 / fp32: the precision of engines and modules built without an explicit one"),
+    "M2M_LIB_PATH": (None, "import of _lib", "load another build of libm2mixer.so (default: the one beside the package)"),
+    "M2M_DIST_BACKEND": (None, "parallel.init_from_env", "torch.distributed backend (default nccl on GPUs; gloo: several ranks on one GPU)"),
+    "M2M_FUSED_UPDATE": (None, "engine construction", "1 / 0 force Adam + operand re-pack as one launch / as two; unset: one launch"),
+    "M2M_CONCURRENT": ("1", "engine construction", "0: every launch on the main stream, no grouped two-tower launches"),
+    "M2M_WGRAD_OVERWRITE": ("1", "engine construction", "weight gradients with a single owner are written, Adam leaves them uncleared"),
+    "M2M_WGRAD_SLOT": ("1", "engine construction", "second row group of a grouped weight-gradient launch into a slot that Adam adds"),
+    "M2M_EARLY_FUSION_WGRAD": ("0", "engine construction", "wide towers: the fusion tower's weight gradients on a side stream"),
+    "M2M_HEADS_POOL": ("1", "engine construction", "wide towers: the heads launch pools the tower outputs itself"),
+    "M2M_DEFER_SMALL": ("1", "engine construction", "the fusion backward's small-gradient slots are reduced by the weight-gradient launch"),
+    "M2M_HEAD_SLOTS": ("1", "engine construction", "the heads' weight gradients through slots (bit-reproducible) instead of float atomics"),
+    "M2M_GROUP_SLOTS": ("1", "engine construction", "the two-tower backward's small gradients through per-workgroup slots"),
+    "M2M_EMBED_FAST": ("1", "engine construction", "patch-embedding weight gradients in the single-owner form (d_x0^T image)"),
+    "M2M_EMBED_FOLD": ("0", "engine construction", "patch embeddings inside the two-tower forward launch"),
+    "M2M_MIMIC_STREAMS": (None, "engine construction", "none / fwd / bwd / both: side streams of the MIMIC step; unset: none up to batch 1024, else both"),
+    "M2M_MIMIC_MERGED_TAIL": ("1", "engine construction", "MIMIC on one stream: one weight-gradient launch, one Adam, one re-pack"),
+    "M2M_MIMIC_EMBED_WGRAD_MERGED": ("1", "engine construction", "MIMIC merged tail: the input projection's weight gradient inside the towers' launch"),
+    "M2M_MLP_RIDE": ("1", "engine construction", "MIMIC: the static MLP's workgroups ride in the time tower's token-mixing launches"),
+    "M2M_CAPTURE_SHARE_SLOTS": ("0", "engine.capture()", "multi-step capture: every step reads the same input slot (diagnostic)"),
+}
+
+
+def switch(name: str, default=None):
+    """The environment's value of a switch in SWITCHES NOW (so a test's monkeypatch.setenv before construction counts), else
+    `default`, else the table's default."""
+    return os.environ.get(name, SWITCHES[name][0] if default is None else default)
+
+
+def switch_on(name: str) -> bool:
+    """Boolean form: a default-on switch is off only for "0", a default-off switch is on only for "1"."""
+    return switch(name) != "0" if SWITCHES[name][0] == "1" else switch(name) == "1"
+
+
 def set_precision(name: str) -> None:
     if name not in L.PREC_BY_NAME:
         raise ValueError(f"precision must be one of {sorted(L.PREC_BY_NAME)}")

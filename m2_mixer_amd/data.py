@@ -115,10 +115,9 @@ def prepare_tail_engine(engine, data: "ResidentAVMnist", split: str, batch_size:
     rem = data.num_samples(split) % batch_size
     if rem == 0:
         return None
-    tails = engine.__dict__.setdefault("_tail_engines", {})
-    if rem not in tails:
-        tails[rem] = engine.sibling(rem)
-    return tails[rem]
+    if rem not in engine._tail_engines:
+        engine._tail_engines[rem] = engine.sibling(rem)
+    return engine._tail_engines[rem]
 
 
 def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train: bool, log_interval_steps: int = 50,
@@ -171,11 +170,11 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
         eng = engine
         if bs != batch_size:                                       # the ragged last batch
             if tail_engine is None:
-                tail_engine = getattr(engine, "_tail_engines", {}).get(bs)
+                tail_engine = engine._tail_engines.get(bs)
             if tail_engine is None:
                 tail_engine = engine.sibling(bs, trains=train)
                 if train:                                          # (an evaluating sibling is not kept as the training one)
-                    engine.__dict__.setdefault("_tail_engines", {})[bs] = tail_engine
+                    engine._tail_engines[bs] = tail_engine
             eng = tail_engine
             eng.pack()                                             # its packed copies missed every step since its last use
             image, audio, labels = image.contiguous(), audio.contiguous(), labels.contiguous()

@@ -11,7 +11,8 @@ What changes relative to the module path (modules/mixer.py + torch autograd):
   * the two modality towers write their outputs straight into their parts of the fused (B, N1+N2, D) buffer
     (ConcatFusion costs nothing) and hand the token means to the heads kernel;
   * the three heads, their losses and gradients are one launch;
-  * each tower's Adam update + operand re-pack follows its own weight gradients on its own HIP stream;
+  * Adam over the whole flat buffer and the re-pack of every operand copy are ONE launch at the end of the step
+    (m2m_adam_pack_all); only the MIMIC step on side streams (large batches) updates and re-packs per parameter segment;
   * the step can be captured into a hipGraph (torch.cuda.CUDAGraph); the dropout step counter, the Adam
     step counter and the learning rate live in device memory so replays stay correct;
   * scores=True: the step also adds its batch's counts into an integer table on the device (ScoreTable, csrc/scores.hip), from
@@ -23,7 +24,6 @@ from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import ctypes as C
-import os
 
 import torch
 
@@ -31,7 +31,8 @@ from . import _lib as L
 from . import config
 from .runtime import (AdamPackPlan, BLOCK_FIELDS, BLOCK_KEYS, EmbedRuntime, MlpRuntime, TowerRuntime, block_param_shapes, heads_bce,
                       heads_ce, can_group, can_group_embeds, can_pack_all, embeds_forward, pack_all,
-                      towers_backward, towers_forward, towers_forward_embeds_ok, towers_wgrad, wgrad_slot_groups)
+                      towers_backward, towers_forward, towers_forward_embeds_ok, towers_wgrad, wgrad_slot_groups,
+                      _embed_ptrs, _grad_ranges, _tower_ptrs)
 
 
 def config_fused_update(n_params: int = 0) -> bool:
@@ -41,7 +42,7 @@ def config_fused_update(n_params: int = 0) -> bool:
     70-78 us against 60-65 us as two launches); with W2 in 8-row x 512-column tiles (2 KiB runs) and the moment streams
     non-temporal it takes 55-56 us and the step 0.4856 against 0.4912 ms (profiles/r04_ab_results.txt r5l-r5n); MM-IMDb
     (2.7 M parameters, latency-bound launches) 0.4602 against 0.4637 ms per step."""
-    env = os.environ.get("M2M_FUSED_UPDATE")
+    env = config.switch("M2M_FUSED_UPDATE")
     if env is not None:
         return env == "1"
     return n_params > 0
@@ -142,6 +143,14 @@ def mimic_param_shapes(cfg: dict) -> "OrderedDict[str, tuple]":
     return s
 
 
+def _exchange_mode(grad_sync) -> str:
+    """How a step exchanges gradients: "none" (grad_sync None: single GPU), "pipelined" (an object with a true `pipelined`:
+    parallel.PipelinedGradSync) or "single" (any other callable(flat_grad) -> scale)."""
+    if grad_sync is None:
+        return "none"
+    return "pipelined" if getattr(grad_sync, "pipelined", False) else "single"
+
+
 def _is_layer_norm(k: str) -> bool:
     return ("layer_norm." in k) or k.endswith("token_mix.0.weight") or k.endswith("token_mix.0.bias") \
         or k.endswith("channel_mix.0.weight") or k.endswith("channel_mix.0.bias")
@@ -197,7 +206,8 @@ class ScoreTable:
 
 class _FlatEngine:
     """Flat parameter / gradient / Adam buffers, the optimizer, data-parallel hooks and hipGraph capture.
-    Subclasses supply `shapes`, `_segment_of(key)`, `_build()`, `_forward(...)`, `_backward(...)`, `pack()`."""
+    Subclasses supply `_param_shapes(cfg)`, `_segment_of(key)`, `_build()` (which names `_towers` and `_embeds`),
+    `_forward(...)`, `_backward(...)`."""
 
     SEGMENTS: Tuple[str, ...] = ()
 
@@ -282,16 +292,21 @@ class _FlatEngine:
         # index ranges of the flat Adam: (lo, n, slot or None, keep)
         self._slot_towers: List[TowerRuntime] = []
         self._ranges_add: list = []
-        self._ranges_keep: list = []
         self._slots_folded = False
+        # every tower / embedding with packed operand copies, named once by _build (pack, the one-launch update)
+        self._towers: List[TowerRuntime] = []
+        self._embeds: List[EmbedRuntime] = []
+        self._fused_heads = False                       # the heads ride in the fusion tower's backward launch (_TwoTowerEngine)
+        self._eval_only = False                         # sibling(..., trains=False)
+        self._tail_engines: Dict[int, "_FlatEngine"] = {}     # training siblings of ragged last batches (data.run_epoch)
         # side streams for the paths whose towers cannot share a launch (wide towers, mixed shapes, the MIMIC static MLP): the
         # second modality runs beside the first.  The AV-MNIST step needs none of them: nine launches on the main stream.
         self.s_b = torch.cuda.Stream(device=dev)
         self.s_fus = torch.cuda.Stream(device=dev)
         self.s_emb = torch.cuda.Stream(device=dev)
-        self.concurrent = os.environ.get("M2M_CONCURRENT", "1") != "0"      # 0: every launch on the main stream (A/B)
+        self.concurrent = config.switch_on("M2M_CONCURRENT")      # 0: every launch on the main stream (A/B)
         self._build()
-        if getattr(self, "_fused_heads", False):
+        if self._fused_heads:
             self._loss_weight_group["fused_heads"] = True
         self.pack()
 
@@ -316,14 +331,14 @@ class _FlatEngine:
           * slot: in a grouped launch a tower that needs two row groups (the fusion tower: twice the rows of its neighbours)
             stores the second group's sums into a slot that the flat Adam adds -- plain stores instead of float atomics.
         M2M_WGRAD_OVERWRITE=0 / M2M_WGRAD_SLOT=0 switch them off (A/B)."""
-        self._slot_towers, self._ranges_add, self._ranges_keep = [], [], []
-        if os.environ.get("M2M_WGRAD_OVERWRITE", "1") == "0":
+        self._slot_towers, self._ranges_add = [], []
+        if not config.switch_on("M2M_WGRAD_OVERWRITE"):
             return
         # `launches`: the towers of each weight-gradient launch of the step (a launch of several towers is the grouped form)
         cand = []                                    # (tower, takes a slot)
         for towers in launches:
             bits = 0
-            if len(towers) > 1 and os.environ.get("M2M_WGRAD_SLOT", "1") != "0":
+            if len(towers) > 1 and config.switch_on("M2M_WGRAD_SLOT"):
                 have = [t.alloc_wslot(self.flat_g) for t in towers]
                 bits = wgrad_slot_groups(towers, self.B) if all(have) else 0
             cand += [(t, bool(bits >> i & 1)) for i, t in enumerate(towers)]
@@ -344,7 +359,11 @@ class _FlatEngine:
                 self._slot_towers.append(t)
             table += [(lo, n, v, 1) for (lo, n), v in zip(rng, views)]
         self._ranges_add = sorted(table, key=lambda r: r[0])
-        self._ranges_keep = [(lo, n, None, k) for lo, n, _, k in self._ranges_add]
+
+    @property
+    def _ranges_keep(self) -> list:
+        """_ranges_add once the slots are folded into flat_g: all that is left is which ranges Adam leaves uncleared."""
+        return [(lo, n, None, k) for lo, n, _, k in self._ranges_add]
 
     def _head(self, name: str, pooled, d_pooled, weight: float, with_grad: bool) -> dict:
         key = "classifier_fusion.classifer." if name == "fusion" else f"classifier_{name}."
@@ -492,35 +511,30 @@ class _FlatEngine:
                                "(or capture again afterwards)")
         for eng, other in ((self, theirs), (sib, mine)):
             eng._ranges_add = [(lo, n, v, int(k and lo in other)) for lo, n, v, k in eng._ranges_add]
-            eng._ranges_keep = [(lo, n, None, k) for lo, n, _, k in eng._ranges_add]
         return sib
 
     # ---- optimizer -------------------------------------------------------------------------------------------
-    def _adam(self, lo: int, hi: int, grad_scale: float, bump: bool, grad_bf16: Optional[torch.Tensor] = None, ranges=None):
-        """Adam over flat elements [lo, hi); clears the gradients it consumes.  grad_bf16: a bf16 copy of the whole flat
-        gradient (the compressed all-reduce result) to take the values from instead of flat_g."""
-        n = hi - lo
-        off = lo * 4
-        tail = (self.adam_state.data_ptr(), self.betas[0], self.betas[1], self.eps, self.weight_decay, -abs(grad_scale), int(bump),
-                L.stream_ptr())
+    def _check_grad_bf16(self, grad_bf16: Optional[torch.Tensor]):
         if grad_bf16 is not None and (grad_bf16.dtype != torch.bfloat16 or grad_bf16.numel() != self.n_params or not grad_bf16.is_cuda):
             raise RuntimeError("grad_bf16 must be a bf16 device copy of the whole flat gradient")
+
+    def _adam(self, lo: int, hi: int, scale: float, grad_bf16: Optional[torch.Tensor] = None, ranges=None):
+        """Adam over flat elements [lo, hi); clears the gradients it consumes.  grad_bf16: a bf16 copy of the whole flat
+        gradient (the compressed all-reduce result) to take the values from instead of flat_g.  ranges: the special gradient
+        ranges inside [lo, hi), indexed from lo."""
+        self._check_grad_bf16(grad_bf16)
+        n = hi - lo
+        p, g, m, v = (t.data_ptr() + lo * 4 for t in (self.flat_p, self.flat_g, self.flat_m, self.flat_v))
+        g16 = 0 if grad_bf16 is None else grad_bf16.data_ptr() + lo * 2
+        # (negative scale: the kernel clears the gradients; the step count was advanced by the step's prologue)
+        tail = (self.adam_state.data_ptr(), self.betas[0], self.betas[1], self.eps, self.weight_decay, -abs(scale), 0)
         if ranges:
-            if lo != 0 or hi != self.n_params:
-                raise RuntimeError("gradient ranges are indexed over the whole flat buffer")
-            arr = (L.GradRange * len(ranges))()
-            for i, (rlo, rn, add, keep) in enumerate(ranges):
-                arr[i].lo, arr[i].n, arr[i].add, arr[i].keep = rlo, rn, L.ptr(add), int(keep)
-            L.check(L.lib().m2m_adam_step_ranges(self.flat_p.data_ptr(), self.flat_g.data_ptr(), L.ptr(grad_bf16), self.flat_m.data_ptr(),
-                                                 self.flat_v.data_ptr(), n, *tail[:-1], arr, len(ranges), tail[-1]), "adam_step_ranges")
-            return
-        if grad_bf16 is None:
-            L.check(L.lib().m2m_adam_step(self.flat_p.data_ptr() + off, self.flat_g.data_ptr() + off, self.flat_m.data_ptr() + off,
-                                          self.flat_v.data_ptr() + off, n, *tail), "adam_step")
+            L.check(L.lib().m2m_adam_step_ranges(p, g, g16, m, v, n, *tail, _grad_ranges(ranges), len(ranges), L.stream_ptr()),
+                    "adam_step_ranges")
+        elif grad_bf16 is None:
+            L.check(L.lib().m2m_adam_step(p, g, m, v, n, *tail, L.stream_ptr()), "adam_step")
         else:
-            L.check(L.lib().m2m_adam_step_bf16(self.flat_p.data_ptr() + off, self.flat_g.data_ptr() + off,
-                                               grad_bf16.data_ptr() + lo * 2, self.flat_m.data_ptr() + off,
-                                               self.flat_v.data_ptr() + off, n, *tail), "adam_step_bf16")
+            L.check(L.lib().m2m_adam_step_bf16(p, g, g16, m, v, n, *tail, L.stream_ptr()), "adam_step_bf16")
 
     def _prologue(self):
         """Head of a training step: Adam step count += 1, dropout counter += 1, losses = 0 -- one tiny launch."""
@@ -533,27 +547,25 @@ class _FlatEngine:
         each element it consumes), so no separate fill pass is needed.  (Channel-mixing weight gradients of the
         overwriting towers -- _setup_wgrad -- are written, not added: those ranges need no clearing.)  On return flat_g
         holds the complete gradient: a row group the weight-gradient launch left in a slot is folded in here."""
-        self._check_trains()
-        self._slots_folded = False
-        self._forward(*batch, training=True, with_grad=True, prologue=True)
-        self._score_forward(batch[-1])
-        self._backward(*batch[:-1])
-        self._score_backward(batch[-1])
+        self._step(batch, fused_update=False)
         for t in self._slot_towers:
             t.wgrad_fold()
         self._slots_folded = True                       # (consumed by the optimizer_step that follows; fused_step resets it)
 
     def fused_step(self, *batch):
         """forward + backward + Adam + re-pack in one go (no gradient exchange: single-GPU training)."""
+        self._step(batch, fused_update=True)
+        return self.losses
+
+    def _step(self, batch, fused_update: bool):
         self._check_trains()
         # (a forward_backward() without its optimizer_step() -- gradient inspection, a skipped step -- must not make THIS step's
         # Adam skip the slot of the two-group tower: the slot is folded by forward_backward only)
         self._slots_folded = False
         self._forward(*batch, training=True, with_grad=True, prologue=True)
         self._score_forward(batch[-1])
-        self._backward(*batch[:-1], fused_update=True)
+        self._backward(*batch[:-1], fused_update=fused_update)
         self._score_backward(batch[-1])
-        return self.losses
 
     # ---- scores ----------------------------------------------------------------------------------------------
     def new_score_table(self) -> ScoreTable:
@@ -574,7 +586,7 @@ class _FlatEngine:
 
     def _preds_in_forward(self) -> bool:
         """Whether a training forward leaves `preds` written (False: the heads ride in the fusion tower's backward launch)."""
-        return not getattr(self, "_fused_heads", False)
+        return not self._fused_heads
 
     def _score_forward(self, truth):
         if self.scores is not None and self._preds_in_forward():
@@ -585,13 +597,23 @@ class _FlatEngine:
             self.scores.add(self.preds, truth)
 
     def _check_trains(self):
-        if getattr(self, "_eval_only", False):
+        if self._eval_only:
             raise RuntimeError("this engine was built with sibling(..., trains=False): it only evaluates")
+
+    def pack(self):
+        """Rebuild the packed MFMA-operand copies from the fp32 masters: every tower and embedding in ONE launch on the main
+        stream (~100 MB of traffic at the HBM roofline on M2-Mixer-B).  Replaced five launches forked over the side streams,
+        whose fork and join edges cost more inside the replayed graph than the concurrency returned."""
+        if can_pack_all(self._towers, self._embeds):
+            pack_all(self._towers, self._embeds)
+            return
+        for m in self._towers + self._embeds:
+            m.pack(force=True)
 
     def _adam_pack_modules(self):
         """(towers, embeds) whose parameters all live in the flat buffers and whose operand copies one m2m_adam_pack_all
         launch can rebuild -- None: the model needs the two-launch form (Adam, then pack())."""
-        return None
+        return (self._towers, self._embeds) if can_pack_all(self._towers, self._embeds) else None
 
     def _update(self, grad_scale: float = 1.0, grad_bf16: Optional[torch.Tensor] = None):
         """Adam over every parameter + operand re-pack.  One launch (m2m_adam_pack_all) where the model allows it: the
@@ -601,14 +623,13 @@ class _FlatEngine:
         ranges = self._ranges_keep if (self._slots_folded or grad_bf16 is not None) else self._ranges_add
         self._slots_folded = False
         if mods is None:
-            self._adam(0, self.n_params, grad_scale, False, grad_bf16, ranges)    # negative scale inside: clears the gradients
+            self._adam(0, self.n_params, grad_scale, grad_bf16, ranges)
             self.pack()
             return
         key = (abs(float(grad_scale)), 0 if grad_bf16 is None else grad_bf16.data_ptr(), tuple((lo, n, 0 if v is None else v.data_ptr(), k) for lo, n, v, k in ranges))
         plan = self._adam_plans.get(key)
         if plan is None:
-            if grad_bf16 is not None and (grad_bf16.dtype != torch.bfloat16 or grad_bf16.numel() != self.n_params or not grad_bf16.is_cuda):
-                raise RuntimeError("grad_bf16 must be a bf16 device copy of the whole flat gradient")
+            self._check_grad_bf16(grad_bf16)
             plan = AdamPackPlan(mods[0], mods[1], self.flat_p, self.flat_g, grad_bf16, self.flat_m, self.flat_v, self.adam_state,
                                 self.betas, self.eps, self.weight_decay, grad_scale, ranges)
             self._adam_plans[key] = plan
@@ -620,14 +641,39 @@ class _FlatEngine:
     def train_step(self, *batch, grad_sync=None):
         """One optimisation step.  grad_sync: optional callable(flat_grad) doing the data-parallel
         all-reduce (parallel.GradSync); it returns the factor the summed gradient must be scaled by."""
-        if grad_sync is None:
-            return self.fused_step(*batch)
-        self.forward_backward(*batch)
-        if getattr(grad_sync, "pipelined", False):
-            self._exchange_and_update_pipelined(grad_sync)
-        else:
-            self.optimizer_step(grad_sync(self.flat_g), getattr(grad_sync, "reduced_bf16", None))
+        self._run_step(grad_sync, *self._phases(batch, grad_sync))
         return self.losses
+
+    # ---- a step in its exchange mode -------------------------------------------------------------------------------------
+    def _run_step(self, grad_sync, first, update) -> float:
+        """One step in grad_sync's exchange mode (_exchange_mode); returns the gradient scale.  first(): everything up to the
+        exchange (the whole step when there is none); update(k, scale): the update behind the exchange -- of chunk k of
+        _update_chunks() when pipelined (chunk k + 1 .. are still on the communication stream), else k = 0: everything.
+        Eager steps pass _phases(), a captured step its graphs' replays."""
+        mode = _exchange_mode(grad_sync)
+        first()
+        if mode == "none":
+            return 1.0
+        if mode == "single":
+            scale = grad_sync(self.flat_g)
+            update(0, scale)
+            return scale
+        chunks = self._update_chunks()
+        scale = grad_sync.start(self.flat_g, [(lo, hi) for lo, hi, _ in chunks])
+        for k in range(len(chunks)):
+            grad_sync.wait(k)
+            update(k, scale)
+        self._slots_folded = False
+        return scale
+
+    def _phases(self, batch, grad_sync):
+        """(first, update) of _run_step for an eager step on `batch`."""
+        mode = _exchange_mode(grad_sync)
+        if mode == "none":
+            return (lambda: self.fused_step(*batch)), None
+        if mode == "single":      # (reduced_bf16 is read behind the exchange: the buffer exists from the first one on)
+            return (lambda: self.forward_backward(*batch)), (lambda k, scale: self.optimizer_step(scale, getattr(grad_sync, "reduced_bf16", None)))
+        return (lambda: self.forward_backward(*batch)), self._update_one_chunk
 
     # ---- exchange pipelined with the optimizer (parallel.PipelinedGradSync) ------------------------------------------------
     def _update_chunks(self):
@@ -644,17 +690,7 @@ class _FlatEngine:
             a, b = max(rlo, lo), min(rlo + rn, hi)
             if a < b:
                 ranges.append((a - lo, b - a, None, keep))
-        n, off = hi - lo, lo * 4
-        tail = (self.adam_state.data_ptr(), self.betas[0], self.betas[1], self.eps, self.weight_decay, -abs(scale), 0)
-        if ranges:
-            arr = (L.GradRange * len(ranges))()
-            for i, (rlo, rn, add, keep) in enumerate(ranges):
-                arr[i].lo, arr[i].n, arr[i].add, arr[i].keep = rlo, rn, None, int(keep)
-            L.check(L.lib().m2m_adam_step_ranges(self.flat_p.data_ptr() + off, self.flat_g.data_ptr() + off, None, self.flat_m.data_ptr() + off,
-                                                 self.flat_v.data_ptr() + off, n, *tail, arr, len(ranges), L.stream_ptr()), "adam_step_ranges")
-        else:
-            L.check(L.lib().m2m_adam_step(self.flat_p.data_ptr() + off, self.flat_g.data_ptr() + off, self.flat_m.data_ptr() + off,
-                                          self.flat_v.data_ptr() + off, n, *tail, L.stream_ptr()), "adam_step")
+        self._adam(lo, hi, scale, None, ranges)
 
     def _update_one_chunk(self, k: int, scale: float):
         lo, hi, mods = self._update_chunks()[k]
@@ -664,17 +700,6 @@ class _FlatEngine:
         else:
             for m in mods:
                 m.pack(force=True)
-
-    def _exchange_and_update_pipelined(self, sync):
-        """all-reduce chunk k + 1 .. on the communication stream while chunk k's Adam + re-pack run here."""
-        if not self._slots_folded:
-            raise RuntimeError("the pipelined update follows forward_backward (which folds the weight-gradient slots)")
-        chunks = self._update_chunks()
-        scale = sync.start(self.flat_g, [(lo, hi) for lo, hi, _ in chunks])
-        for k in range(len(chunks)):
-            sync.wait(k)
-            self._update_one_chunk(k, scale)
-        self._slots_folded = False
 
     # ---- hipGraph capture -----------------------------------------------------------------------------------
     def release_capture(self):
@@ -696,7 +721,7 @@ class _FlatEngine:
             raise ValueError("steps > 1 is only supported without a gradient exchange")
         nb = len(batch)
         slots = [tuple(t.clone() for t in batch) for _ in range(steps)]
-        if steps > 1 and os.environ.get("M2M_CAPTURE_SHARE_SLOTS", "0") == "1":
+        if steps > 1 and config.switch_on("M2M_CAPTURE_SHARE_SLOTS"):
             slots = [slots[0]] * steps                  # diagnostic (scripts/spg_probe.sh): every step reads the SAME (cache-resident) batch
         self._static = slots[0] if steps == 1 else slots
         st = slots[0]
@@ -709,66 +734,48 @@ class _FlatEngine:
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
-            scale = 1.0
+            first, update = self._phases(st, grad_sync)
             for _ in range(2):                       # warm-up: lazy inits (LDS attributes, allocations) happen here
-                if grad_sync is None:
-                    self.fused_step(*st)
-                elif getattr(grad_sync, "pipelined", False):
-                    self.forward_backward(*st)
-                    self._exchange_and_update_pipelined(grad_sync)
-                    scale = 1.0 / getattr(grad_sync, "world", 1)
-                else:
-                    self.forward_backward(*st)
-                    scale = grad_sync(self.flat_g)
-                    self.optimizer_step(scale, getattr(grad_sync, "reduced_bf16", None))
+                scale = self._run_step(grad_sync, first, update)
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
         for dst, src in zip(state, snap):
             dst.copy_(src)
         self.pack()
         torch.cuda.synchronize()
-        # thread_local capture mode: a data-parallel process has other threads (the RCCL watchdog) that may touch the HIP
-        # runtime while this thread captures; only this thread's calls belong to the graph
-        g1 = torch.cuda.CUDAGraph()
+
+        def graph_of(fn):
+            # thread_local capture mode: a data-parallel process has other threads (the RCCL watchdog) that may touch the HIP
+            # runtime while this thread captures; only this thread's calls belong to the graph
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                fn()
+            return g
+
         out_losses = self.losses
-        if grad_sync is None:
-            if steps > 1:
-                # per-step output slots of THIS graph; the engine's own losses / logits / preds stay what they were (other
-                # captured graphs and evaluate() write those)
-                home = (self.losses, self.logits, self.preds)
-                self.losses_steps = torch.zeros(steps, *self.losses.shape, device=self.device)
-                self.logits_steps = torch.zeros(steps, *self.logits.shape, device=self.device)
-                self.preds_steps = torch.zeros(steps, *self.preds.shape, dtype=self.preds.dtype, device=self.device)
-                out_losses = self.losses_steps
-            with torch.cuda.graph(g1, capture_error_mode="thread_local"):
+        if steps > 1:
+            # per-step output slots of THIS graph; the engine's own losses / logits / preds stay what they were (other
+            # captured graphs and evaluate() write those)
+            home = (self.losses, self.logits, self.preds)
+            self.losses_steps = torch.zeros(steps, *self.losses.shape, device=self.device)
+            self.logits_steps = torch.zeros(steps, *self.logits.shape, device=self.device)
+            self.preds_steps = torch.zeros(steps, *self.preds.shape, dtype=self.preds.dtype, device=self.device)
+            out_losses = self.losses_steps
+
+            def all_steps():
                 for i in range(steps):
-                    if steps > 1:
-                        self.losses, self.logits, self.preds = self.losses_steps[i], self.logits_steps[i], self.preds_steps[i]
+                    self.losses, self.logits, self.preds = self.losses_steps[i], self.logits_steps[i], self.preds_steps[i]
                     self.fused_step(*slots[i])
-            if steps > 1:
-                self.losses, self.logits, self.preds = home
-            graphs = (g1,)
-        elif getattr(grad_sync, "pipelined", False):
-            # forward + backward | per chunk: [its all-reduce lands] its Adam + re-pack (one small graph per chunk)
-            with torch.cuda.graph(g1, capture_error_mode="thread_local"):
-                self.forward_backward(*st)
-            chunk_graphs = []
-            for k in range(len(self._update_chunks())):
-                gk = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(gk, capture_error_mode="thread_local"):
-                    self._update_one_chunk(k, scale)
-                chunk_graphs.append(gk)
-            self._slots_folded = False
-            graphs = (g1, *chunk_graphs)
-        else:
-            g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g1, capture_error_mode="thread_local"):
-                self.forward_backward(*st)
-            with torch.cuda.graph(g2, capture_error_mode="thread_local"):
-                self.optimizer_step(scale, getattr(grad_sync, "reduced_bf16", None))   # (the buffer exists since the warm-up)
-            graphs = (g1, g2)
+
+            first = all_steps
+        # forward + backward (no exchange: the whole step, `steps` times) | [the all-reduce lands] Adam + re-pack: one graph, or one
+        # small graph per chunk when pipelined (the scale, and a bf16 exchange's buffer, exist since the warm-up)
+        nupd = {"none": 0, "single": 1, "pipelined": len(self._update_chunks())}[_exchange_mode(grad_sync)]
+        graphs = (graph_of(first), *[graph_of(lambda k=k: update(k, scale)) for k in range(nupd)])
+        if steps > 1:
+            self.losses, self.logits, self.preds = home
+        self._slots_folded = False
         self._graph = graphs
-        pipelined = grad_sync is not None and getattr(grad_sync, "pipelined", False)
 
         def replay(*new_batch):
             if new_batch and new_batch[0] is not None:
@@ -777,15 +784,7 @@ class _FlatEngine:
                 for i in range(steps):
                     for dst, src in zip(slots[i], new_batch[i * nb:(i + 1) * nb]):
                         dst.copy_(src, non_blocking=True)
-            graphs[0].replay()
-            if pipelined:
-                grad_sync.start(self.flat_g, [(lo, hi) for lo, hi, _ in self._update_chunks()])
-                for k in range(len(graphs) - 1):
-                    grad_sync.wait(k)
-                    graphs[1 + k].replay()
-            elif grad_sync is not None:
-                grad_sync(self.flat_g)
-                graphs[1].replay()
+            self._run_step(grad_sync, graphs[0].replay, lambda k, scale: graphs[1 + k].replay())
             return out_losses                     # this graph's own buffer: (4,) or, for a multi-step graph, (steps, 4)
 
         replay.losses = out_losses
@@ -834,6 +833,7 @@ class _TwoTowerEngine(_FlatEngine):
 
         self.e_a = make_embed(f"{a}_mixer.", ca)
         self.e_b = make_embed(f"{b}_mixer.", cb)
+        self._towers, self._embeds = [self.t_a, self.t_b, self.t_fus], [self.e_a, self.e_b]
         B, D, dev = self.B, self.D, self.device
         f = lambda *s: torch.zeros(*s, device=dev)
         # embedding outputs; a long-K embedding (audio) is computed as k-split partial sums that the tower launch adds
@@ -853,44 +853,40 @@ class _TwoTowerEngine(_FlatEngine):
         # cfg batch: 0.555 ms against 0.502 ms merged -- the extra fork / join of the replayed graph and a single-tower launch
         # without its slot (80 steps) cost more than the shorter tail returns.  Off.
         self._early_fus_wgrad = (self.concurrent and self.t_fus.wide and B * self.Nf <= 8192 and
-                                 os.environ.get("M2M_EARLY_FUSION_WGRAD", "0") == "1")
+                                 config.switch_on("M2M_EARLY_FUSION_WGRAD"))
         self._setup_wgrad([[self.t_fus], [self.t_a, self.t_b]] if self._early_fus_wgrad else [[self.t_fus, self.t_a, self.t_b]])
         self._fused_heads = self._heads_are_ce() and self.t_fus.backward_heads_ok(B, 3, self.K)
         # Wide towers (MM-IMDb): their forward cannot pool inside the chain launch (a workgroup does not own whole samples) and
         # appends a token-mean launch; the heads kernel pools the tower outputs itself instead (m2m_head.tokens): two launches less.
-        self._heads_pool = (self.t_a.wide and self.t_b.wide and self.t_fus.wide and os.environ.get("M2M_HEADS_POOL", "1") != "0")
+        self._heads_pool = (self.t_a.wide and self.t_b.wide and self.t_fus.wide and config.switch_on("M2M_HEADS_POOL"))
         # the fusion tower's backward is always followed by the weight-gradient launch (_backward): the reduction of its
         # small-gradient slots rides there instead of being a launch between the two backward launches (M2M_DEFER_SMALL=0: A/B)
-        self.t_fus.set_wgrad_reduces_small(not self._fused_heads and os.environ.get("M2M_DEFER_SMALL", "1") != "0")
+        self.t_fus.set_wgrad_reduces_small(not self._fused_heads and config.switch_on("M2M_DEFER_SMALL"))
         # the heads' weight gradients: per-workgroup slots added in a fixed order by the weight-gradient launch instead of float
         # atomics -- with them a bf16 step is bit-reproducible (M2M_HEAD_SLOTS=0: atomics)
         self._head_part, self._wgrad_heads = None, None
-        if (self._heads_are_ce() and not self._fused_heads and os.environ.get("M2M_HEAD_SLOTS", "1") != "0"
+        if (self._heads_are_ce() and not self._fused_heads and config.switch_on("M2M_HEAD_SLOTS")
                 and self.K * D + self.K + 2 <= L.SPLIT_GPART):
             self._head_part = torch.zeros(3, int(L.lib().m2m_heads_part_tiles(B)), L.SPLIT_GPART, device=dev)
         # the two modality towers' backward launch: slots instead of 128-way contended float atomics for the small gradients,
         # their reduction in the weight-gradient launch as well (M2M_GROUP_SLOTS=0: atomics, A/B)
-        if (os.environ.get("M2M_GROUP_SLOTS", "1") != "0" and self.t_a.has_small_slots() and self.t_b.has_small_slots()
+        if (config.switch_on("M2M_GROUP_SLOTS") and self.t_a.has_small_slots() and self.t_b.has_small_slots()
                 and can_group(self.t_a, self.t_b, self.B)):
             for t in (self.t_a, self.t_b):
                 t.set_wgrad_group_slots(True)
                 t.set_wgrad_reduces_small(True)
         # the embeddings' weight gradients in their single-owner form: the tower backward leaves d_x0^T as packed blocks
         self._embed_towers = []
-        if os.environ.get("M2M_EMBED_FAST", "1") != "0" and self.t_a.enable_dx0_image(B) and self.t_b.enable_dx0_image(B):
+        if config.switch_on("M2M_EMBED_FAST") and self.t_a.enable_dx0_image(B) and self.t_b.enable_dx0_image(B):
             self._embed_towers = [self.t_a, self.t_b]
             # their weight gradients are then written ("="), and Adam leaves those ranges uncleared -- if the range table has room
-            import ctypes as C
-            ep = (C.POINTER(L.Embed) * 2)(C.pointer(self.e_a.desc), C.pointer(self.e_b.desc))
-            tp = (C.POINTER(L.Tower) * 2)(C.pointer(self.t_a.desc), C.pointer(self.t_b.desc))
-            fast = bool(L.lib().m2m_embeds_wgrad_form(ep, tp, 2, B))
-            if fast and os.environ.get("M2M_WGRAD_OVERWRITE", "1") != "0" and len(self._ranges_add) + 2 <= L.MAX_GRAD_RANGES:
+            fast = bool(L.lib().m2m_embeds_wgrad_form(_embed_ptrs(self._embeds), _tower_ptrs(self._embed_towers), 2, B))
+            if fast and config.switch_on("M2M_WGRAD_OVERWRITE") and len(self._ranges_add) + 2 <= L.MAX_GRAD_RANGES:
                 for e, pre in ((self.e_a, f"{a}_mixer."), (self.e_b, f"{b}_mixer.")):
                     gw = self.grads[pre + "to_patch_embedding.0.weight"]
                     e.set_wgrad_overwrite(True)
                     self._ranges_add.append(((gw.data_ptr() - self.flat_g.data_ptr()) // 4, gw.numel(), None, 1))
                 self._ranges_add.sort(key=lambda r: r[0])
-                self._ranges_keep = [(lo, n, None, k) for lo, n, _, k in self._ranges_add]
 
         # Patch embeddings inside the two-tower forward launch (m2m_towers_forward_embeds: -1 launch at the head of the step).
         # The step head then splits: losses = 0 / Adam step += 1 ride in that launch, the dropout counter -- which that launch
@@ -901,7 +897,7 @@ class _TwoTowerEngine(_FlatEngine):
         # 0.5116-0.5163 against 0.5067-0.5121 ms -- the audio tower's 128 workgroups each stream the whole 800 KB embedding
         # weight + 200 KB of input alone (+19 us, not the 7.5 us the CU's 64 B/clk would allow) while the image tower's 128 CUs
         # wait; the launch of its own spreads that work over 256 + 128 workgroups (k-split).  Parity-green either way.
-        self._embed_fold = (os.environ.get("M2M_EMBED_FOLD", "0") == "1" and grouped and self.concurrent and not self._early_fus_wgrad
+        self._embed_fold = (config.switch_on("M2M_EMBED_FOLD") and grouped and self.concurrent and not self._early_fus_wgrad
                             and self.x0_splits is not None and self.e_a.prec == self.t_a.prec and self.e_a.D == self.t_a.D
                             and towers_forward_embeds_ok([self.t_a, self.t_b], [self.e_a, self.e_b], B)
                             and self.t_a.wgrad_form(B) == 0 and self.t_fus.wgrad_form(B) == 0)
@@ -972,17 +968,6 @@ class _TwoTowerEngine(_FlatEngine):
 
     def _preds_shape(self):
         return (3, self.B)
-
-    def pack(self):
-        """Rebuild the packed MFMA-operand copies from the fp32 masters: every tower and both embeddings in ONE launch
-        on the main stream (~100 MB of traffic at the HBM roofline).  Replaced five launches forked over the side
-        streams, whose fork and join edges cost more inside the replayed graph than the concurrency returned."""
-        towers, embeds = [self.t_a, self.t_b, self.t_fus], [self.e_a, self.e_b]
-        if can_pack_all(towers, embeds):
-            pack_all(towers, embeds)
-            return
-        for m in towers + embeds:
-            m.pack(force=True)
 
     def _loss_heads(self, heads, labels, zero_losses):
         raise NotImplementedError
@@ -1122,10 +1107,6 @@ class _TwoTowerEngine(_FlatEngine):
             main.wait_stream(s_f)
         if fused_update:
             self._update(1.0)
-
-    def _adam_pack_modules(self):
-        towers, embeds = [self.t_a, self.t_b, self.t_fus], [self.e_a, self.e_b]
-        return (towers, embeds) if can_pack_all(towers, embeds) else None
 
     def _update_chunks(self):
         """One chunk per parameter segment, in flat order: modality a (its patch embedding + tower), modality b, fusion tower
@@ -1269,18 +1250,21 @@ class MimicEngine(_FlatEngine):
         # every fork / join edge of the replayed graph costs ~5 us, the launches they hide are 5-30 us at the cfg batch:
         # measured 0.230 ms on one stream against 0.255 ms on three (fwd only 0.257, bwd only 0.25-0.27); at batch 8192 the
         # launches are long enough: 2.445 ms on three streams against 2.492 on one.  M2M_MIMIC_STREAMS=fwd|bwd|both|none (A/B).
-        mode = os.environ.get("M2M_MIMIC_STREAMS", "none" if self.B <= 1024 else "both")
-        self._merged_tail = os.environ.get("M2M_MIMIC_MERGED_TAIL", "1") != "0"          # (A/B)
+        mode = config.switch("M2M_MIMIC_STREAMS", "none" if self.B <= 1024 else "both")
+        self._merged_tail = config.switch_on("M2M_MIMIC_MERGED_TAIL")          # (A/B)
+        # merged tail: the input projection's weight gradient in the towers' weight-gradient launch (one launch less)
+        self._embed_wgrad_merged = config.switch_on("M2M_MIMIC_EMBED_WGRAD_MERGED")
         self._conc_fwd, self._conc_bwd = mode in ("fwd", "both"), mode in ("bwd", "both")
-        self._heads_pool = os.environ.get("M2M_HEADS_POOL", "1") != "0"       # (both towers are wide: N = 24 / 25)
+        self._heads_pool = config.switch_on("M2M_HEADS_POOL")       # (both towers are wide: N = 24 / 25)
         # the static MLP's two launches as extra workgroups of the time tower's token-mixing launches (MlpRuntime.forward_ride)
-        self._mlp_ride = os.environ.get("M2M_MLP_RIDE", "1") != "0" and self.B <= 2048
+        self._mlp_ride = config.switch_on("M2M_MLP_RIDE") and self.B <= 2048
         self.t_time = self._make_tower("time_mixer.", ct, self.Nt, 0)
         self.t_fus = self._make_tower("fusion_mixer.", cm, self.Nf, 2048)
         # (B, N, K) rows == a (B, 1, N, K) image cut into (1, K) patches
         self.e_time = EmbedRuntime(1, self.Nt, ct["embedding_dim"], 1, ct["embedding_dim"], self.D, self.prec)
         self.e_time.bind_params(self.params["time_mixer.proj.weight"], self.params["time_mixer.proj.bias"])
         self.e_time.bind_grads(self.grads["time_mixer.proj.weight"], self.grads["time_mixer.proj.bias"])
+        self._towers, self._embeds = [self.t_time, self.t_fus], [self.e_time]
         nb = cs["num_blocks"]
         keys = [f"static_extractor.module_list.{3 * i}." for i in range(nb)] + [f"static_extractor.module_list.{3 * nb}."]
         self.mlp = MlpRuntime([cs["input_dim"]] + [cs["hidden_dim"]] * nb + [cs["output_dim"]], True, self.p_drop, 4096)
@@ -1295,18 +1279,6 @@ class MimicEngine(_FlatEngine):
         self.d_fused = f(B, self.Nf, D)
         self.dx0_time = f(B * self.Nt, D)
         self.preds = torch.zeros(3, B, dtype=torch.int32, device=dev)
-
-    def pack(self):
-        towers, embeds = [self.t_time, self.t_fus], [self.e_time]
-        if can_pack_all(towers, embeds):
-            pack_all(towers, embeds)
-            return
-        for m in towers + embeds:
-            m.pack(force=True)
-
-    def _adam_pack_modules(self):
-        towers, embeds = [self.t_time, self.t_fus], [self.e_time]
-        return (towers, embeds) if can_pack_all(towers, embeds) else None
 
     def _forward(self, static, time, labels, training: bool, with_grad: bool, prologue: bool = False):
         B, D = self.B, self.D
@@ -1357,8 +1329,7 @@ class MimicEngine(_FlatEngine):
             self.t_time.backward(B, d_time_part, fs, self.dpool_time, self.dx0_time, self.Nt * D, self.seed, 0, sd)
             if self._mlp_ride:
                 self.mlp.ride_flush()
-            if os.environ.get("M2M_MIMIC_EMBED_WGRAD_MERGED", "1") != "0":
-                # the input projection's weight gradient in the towers' weight-gradient launch (one launch less)
+            if self._embed_wgrad_merged:
                 towers_wgrad([self.t_fus, self.t_time], B, embeds=[self.e_time], inputs=[time], d_x0s=[self.dx0_time],
                              seed=self.seed, step=0, step_dev=sd)
             else:
@@ -1373,17 +1344,17 @@ class MimicEngine(_FlatEngine):
         with torch.cuda.stream(s_b):                        # static MLP: gradient of token 0 + of its own head
             self.mlp.backward(static, B, self.d_fused, fs, self.dpool_static)
             if fused_update:
-                self._adam(*self.segments["static"], 1.0, False)
+                self._adam(*self.segments["static"], 1.0)
         with torch.cuda.stream(s_f):
             self.t_fus.wgrad(B, self.seed, 0, sd)
             if fused_update:
-                self._adam(*self.segments["fusion"], 1.0, False)
+                self._adam(*self.segments["fusion"], 1.0)
                 self.t_fus.pack(force=True)
         self.t_time.backward(B, d_time_part, fs, self.dpool_time, self.dx0_time, self.Nt * D, self.seed, 0, sd)
         self.t_time.wgrad(B, self.seed, 0, sd)
         self.e_time.wgrad(time, self.dx0_time, B)
         if fused_update:
-            self._adam(*self.segments["time"], 1.0, False)
+            self._adam(*self.segments["time"], 1.0)
             self.t_time.pack(force=True)
             self.e_time.pack(force=True)
         main.wait_stream(s_b)

@@ -36,6 +36,46 @@ def _check_tensor(t: torch.Tensor, shape, name: str):
         raise RuntimeError(f"{name}: expected contiguous float32 {tuple(shape)}, got {t.dtype} {tuple(t.shape)}")
 
 
+# ---- one helper per ctypes idiom: every launch below (and engine.py) builds its arguments with these ------------------------
+def _tower_ptrs(towers):
+    """Array of pointers to the towers' descriptors (no tower: one NULL element)."""
+    return (C.POINTER(L.Tower) * max(len(towers), 1))(*[C.pointer(t.desc) for t in towers])
+
+
+def _embed_ptrs(embeds):
+    """Array of pointers to the embeddings' descriptors (no embedding: one NULL element)."""
+    return (C.POINTER(L.Embed) * max(len(embeds), 1))(*[C.pointer(e.desc) for e in embeds])
+
+
+def _data_ptrs(tensors):
+    """Array of the tensors' device pointers (no tensor: one NULL element)."""
+    return (C.c_void_p * max(len(tensors), 1))(*[t.data_ptr() for t in tensors])
+
+
+def _device_descs(towers):
+    """Array of the device pointers of the towers' descriptor copies (TowerRuntime.device_desc)."""
+    return (C.c_void_p * max(len(towers), 1))(*[t.device_desc() for t in towers])
+
+
+def _grad_ranges(ranges):
+    """L.GradRange array of [(lo, n, slot tensor or None, keep), ...] (no range: one zeroed element)."""
+    arr = (L.GradRange * max(len(ranges), 1))()
+    for i, (lo, n, add, keep) in enumerate(ranges):
+        arr[i].lo, arr[i].n, arr[i].add, arr[i].keep = lo, n, L.ptr(add), int(keep)
+    return arr
+
+
+def _step_head(adam_state, losses, drop_counter=None):
+    """Reference to an L.StepHead: Adam step count += 1, losses = 0 and, given its counter, dropout step += 1 at the head of a
+    launch."""
+    return C.byref(L.StepHead(L.ptr(adam_state), L.ptr(drop_counter), L.ptr(losses), int(losses.numel())))
+
+
+def _drop_tail(seed: int, step: int, step_dev: Optional[torch.Tensor] = None):
+    """(seed, step, device step counter or NULL, stream): the dropout stream of a launch that draws masks, then its HIP stream."""
+    return seed & 0xFFFFFFFF, step & 0xFFFFFFFF, L.ptr(step_dev), L.stream_ptr()
+
+
 class TowerRuntime:
     """One m2m_tower: `nblocks` MixerBlocks (+ final LayerNorm) over (B, N, D) tokens."""
 
@@ -270,14 +310,12 @@ class TowerRuntime:
             self.ensure_buffers(B)
         self.ensure_workspace(B)
         L.check(L.lib().m2m_tower_forward(C.byref(self.desc), x0.data_ptr(), x0_ss, B, out.data_ptr(), out_ss,
-                                          L.ptr(pooled), int(training), seed & 0xFFFFFFFF, step & 0xFFFFFFFF,
-                                          L.ptr(step_dev), L.stream_ptr()), "tower_forward")
+                                          L.ptr(pooled), int(training), *_drop_tail(seed, step, step_dev)), "tower_forward")
 
     def backward(self, B: int, d_out: Optional[torch.Tensor], d_out_ss: int, d_pooled: Optional[torch.Tensor],
                  d_x0: torch.Tensor, d_x0_ss: int, seed: int, step: int, step_dev: Optional[torch.Tensor] = None):
         L.check(L.lib().m2m_tower_backward(C.byref(self.desc), B, L.ptr(d_out), d_out_ss, L.ptr(d_pooled),
-                                           d_x0.data_ptr(), d_x0_ss, seed & 0xFFFFFFFF, step & 0xFFFFFFFF,
-                                           L.ptr(step_dev), L.stream_ptr()), "tower_backward")
+                                           d_x0.data_ptr(), d_x0_ss, *_drop_tail(seed, step, step_dev)), "tower_backward")
 
     def enable_dx0_image(self, B: int) -> bool:
         """Let the backward also leave d_x0^T as packed operand blocks (m2m_tower.dx0_chn): the patch-embedding weight
@@ -371,12 +409,11 @@ class TowerRuntime:
         arr = _head_array(heads)
         logits, losses, preds = out
         L.check(L.lib().m2m_tower_backward_heads(C.byref(self.desc), B, arr, len(heads), own, labels.data_ptr(), K, logits.data_ptr(),
-                                                 losses.data_ptr(), preds.data_ptr(), d_x0.data_ptr(), d_x0_ss, seed & 0xFFFFFFFF,
-                                                 step & 0xFFFFFFFF, L.ptr(step_dev), L.stream_ptr()), "tower_backward_heads")
+                                                 losses.data_ptr(), preds.data_ptr(), d_x0.data_ptr(), d_x0_ss,
+                                                 *_drop_tail(seed, step, step_dev)), "tower_backward_heads")
 
     def wgrad(self, B: int, seed: int, step: int, step_dev: Optional[torch.Tensor] = None):
-        L.check(L.lib().m2m_tower_wgrad(C.byref(self.desc), B, seed & 0xFFFFFFFF, step & 0xFFFFFFFF, L.ptr(step_dev),
-                                        L.stream_ptr()), "tower_wgrad")
+        L.check(L.lib().m2m_tower_wgrad(C.byref(self.desc), B, *_drop_tail(seed, step, step_dev)), "tower_wgrad")
 
     def device_desc(self) -> int:
         """Device pointer of a byte copy of the descriptor (for the multi-tower launches, whose kernel arguments cannot
@@ -392,8 +429,8 @@ class TowerRuntime:
         """Keep-mask (uint8) of one dropout site in the kernels' index order (test hook)."""
         n = {0: B * self.D * self.T, 1: B * self.D * self.N, 2: B * self.N * self.Cp, 3: B * self.N * self.D}[site]
         m = torch.empty(n, dtype=torch.uint8, device=self.device)
-        L.check(L.lib().m2m_dropout_mask(C.byref(self.desc), blk, site, B, seed & 0xFFFFFFFF, step & 0xFFFFFFFF,
-                                         m.data_ptr(), L.stream_ptr()), "dropout_mask")
+        L.check(L.lib().m2m_dropout_mask(C.byref(self.desc), blk, site, B, *_drop_tail(seed, step)[:2], m.data_ptr(), L.stream_ptr()),
+                "dropout_mask")
         return m
 
 
@@ -408,10 +445,7 @@ def can_group(a: TowerRuntime, b: TowerRuntime, B: Optional[int] = None) -> bool
 
 def towers_forward_embeds_ok(towers: Sequence[TowerRuntime], embeds: Sequence["EmbedRuntime"], B: int) -> bool:
     """towers_forward(..., embeds=, inputs=) takes this pair: the patch embeddings ride in the towers' launch."""
-    n = len(towers)
-    host = (C.POINTER(L.Tower) * n)(*[C.pointer(t.desc) for t in towers])
-    ep = (C.POINTER(L.Embed) * n)(*[C.pointer(e.desc) for e in embeds])
-    return bool(L.lib().m2m_towers_forward_embeds_ok(host, n, ep, B))
+    return bool(L.lib().m2m_towers_forward_embeds_ok(_tower_ptrs(towers), len(towers), _embed_ptrs(embeds), B))
 
 
 def towers_forward(towers: Sequence[TowerRuntime], ios: Sequence[tuple], B: int, training: bool, seed: int, step: int,
@@ -426,44 +460,33 @@ def towers_forward(towers: Sequence[TowerRuntime], ios: Sequence[tuple], B: int,
         if training:
             t.ensure_buffers(B)
         t.ensure_workspace(B)
-    host = (C.POINTER(L.Tower) * n)(*[C.pointer(t.desc) for t in towers])
+    host = _tower_ptrs(towers)
     io = (L.TowerIO * n)()
     for i, (x0, x0_ss, out, out_ss, pooled, *parts) in enumerate(ios):
         io[i].x0, io[i].x0_ss, io[i].out, io[i].out_ss, io[i].pooled = x0.data_ptr(), x0_ss, out.data_ptr(), out_ss, L.ptr(pooled)
         io[i].x0_parts, io[i].x0_part_stride = parts if parts else (1, 0)
     if len(embeds):
-        ep = (C.POINTER(L.Embed) * n)(*[C.pointer(e.desc) for e in embeds])
-        ip = (C.c_void_p * n)(*[t.data_ptr() for t in inputs])
-        hd = None
-        if head is not None:
-            hd = L.StepHead()
-            hd.adam_state, hd.drop_counter, hd.losses, hd.nlosses = L.ptr(head[0]), None, L.ptr(head[1]), int(head[1].numel())
-        L.check(L.lib().m2m_towers_forward_embeds(host, io, n, ep, ip, C.byref(hd) if hd is not None else None, B, int(training),
-                                                  seed & 0xFFFFFFFF, step & 0xFFFFFFFF, L.ptr(step_dev), L.stream_ptr()),
-                "towers_forward_embeds")
+        hd = _step_head(*head) if head is not None else None
+        L.check(L.lib().m2m_towers_forward_embeds(host, io, n, _embed_ptrs(embeds), _data_ptrs(inputs), hd, B, int(training),
+                                                  *_drop_tail(seed, step, step_dev)), "towers_forward_embeds")
         return
-    L.check(L.lib().m2m_towers_forward(host, io, n, B, int(training), seed & 0xFFFFFFFF, step & 0xFFFFFFFF, L.ptr(step_dev),
-                                       L.stream_ptr()), "towers_forward")
+    L.check(L.lib().m2m_towers_forward(host, io, n, B, int(training), *_drop_tail(seed, step, step_dev)), "towers_forward")
 
 
 def towers_backward(towers: Sequence[TowerRuntime], ios: Sequence[tuple], B: int, seed: int, step: int,
                     step_dev: Optional[torch.Tensor] = None):
     """ios[i] = (d_out or None, d_out_ss, d_pooled or None, d_x0, d_x0_ss): two towers, one launch."""
     n = len(towers)
-    host = (C.POINTER(L.Tower) * n)(*[C.pointer(t.desc) for t in towers])
     io = (L.TowerGIO * n)()
     for i, (d_out, d_out_ss, d_pooled, d_x0, d_x0_ss) in enumerate(ios):
         io[i].d_out, io[i].d_out_ss, io[i].d_pooled = L.ptr(d_out), d_out_ss, L.ptr(d_pooled)
         io[i].d_x0, io[i].d_x0_ss = d_x0.data_ptr(), d_x0_ss
-    L.check(L.lib().m2m_towers_backward(host, io, n, B, seed & 0xFFFFFFFF, step & 0xFFFFFFFF, L.ptr(step_dev), L.stream_ptr()),
-            "towers_backward")
+    L.check(L.lib().m2m_towers_backward(_tower_ptrs(towers), io, n, B, *_drop_tail(seed, step, step_dev)), "towers_backward")
 
 
 def wgrad_slot_groups(towers: Sequence[TowerRuntime], B: int) -> int:
     """bit i: towers_wgrad(towers, B) leaves tower i's second row group in its slot (TowerRuntime.alloc_wslot)."""
-    n = len(towers)
-    host = (C.POINTER(L.Tower) * n)(*[C.pointer(t.desc) for t in towers])
-    return int(L.lib().m2m_wgrad_slot_groups(host, n, B))
+    return int(L.lib().m2m_wgrad_slot_groups(_tower_ptrs(towers), len(towers), B))
 
 
 def towers_wgrad(towers: Sequence[TowerRuntime], B: int, embeds: Sequence["EmbedRuntime"] = (),
@@ -477,25 +500,20 @@ def towers_wgrad(towers: Sequence[TowerRuntime], B: int, embeds: Sequence["Embed
     single-owner form (no atomics).
     heads (dicts as for heads_ce, each with "g_part") + K: the launch also adds the heads' per-workgroup weight-gradient sums."""
     n, ne = len(towers), len(embeds)
-    host = (C.POINTER(L.Tower) * n)(*[C.pointer(t.desc) for t in towers])
-    dev = (C.c_void_p * n)(*[t.device_desc() for t in towers])
-    ep = (C.POINTER(L.Embed) * max(ne, 1))(*[C.pointer(e.desc) for e in embeds])
-    ip = (C.c_void_p * max(ne, 1))(*[t.data_ptr() for t in inputs])
-    dp = (C.c_void_p * max(ne, 1))(*[t.data_ptr() for t in d_x0s])
-    et = (C.POINTER(L.Tower) * max(ne, 1))(*[C.pointer(t.desc) for t in embed_towers]) if len(embed_towers) == ne and ne else None
+    et = _tower_ptrs(embed_towers) if len(embed_towers) == ne and ne else None
+    # (everything up to the device step counter is common to the three entry points)
+    args = (_tower_ptrs(towers), _device_descs(towers), n, _embed_ptrs(embeds), _data_ptrs(inputs), _data_ptrs(d_x0s), et, ne, B,
+            *_drop_tail(seed, step, step_dev)[:3])
     if bump is not None:
         # the step's dropout counter advances in this launch, behind its last reader (m2m_towers_wgrad_tail)
-        L.check(L.lib().m2m_towers_wgrad_tail(host, dev, n, ep, ip, dp, et, ne, B, seed & 0xFFFFFFFF, step & 0xFFFFFFFF,
-                                              L.ptr(step_dev), _head_array(heads) if heads else None, len(heads) if heads else 0, K,
+        L.check(L.lib().m2m_towers_wgrad_tail(*args, _head_array(heads) if heads else None, len(heads) if heads else 0, K,
                                               bump.data_ptr(), L.stream_ptr()), "towers_wgrad_tail")
         return
     if heads:
         # the classification heads' weight-gradient slots (heads_ce with "g_part") are added to g_w / g_b by this launch
-        L.check(L.lib().m2m_towers_wgrad_heads(host, dev, n, ep, ip, dp, et, ne, B, seed & 0xFFFFFFFF, step & 0xFFFFFFFF,
-                                               L.ptr(step_dev), _head_array(heads), len(heads), K, L.stream_ptr()), "towers_wgrad_heads")
+        L.check(L.lib().m2m_towers_wgrad_heads(*args, _head_array(heads), len(heads), K, L.stream_ptr()), "towers_wgrad_heads")
         return
-    L.check(L.lib().m2m_towers_wgrad(host, dev, n, ep, ip, dp, et, ne, B, seed & 0xFFFFFFFF, step & 0xFFFFFFFF, L.ptr(step_dev),
-                                     L.stream_ptr()), "towers_wgrad")
+    L.check(L.lib().m2m_towers_wgrad(*args, L.stream_ptr()), "towers_wgrad")
 
 
 def can_pack_all(towers: Sequence[TowerRuntime], embeds: Sequence["EmbedRuntime"]) -> bool:
@@ -505,10 +523,7 @@ def can_pack_all(towers: Sequence[TowerRuntime], embeds: Sequence["EmbedRuntime"
 
 def pack_all(towers: Sequence[TowerRuntime], embeds: Sequence["EmbedRuntime"]):
     """Every packed operand copy of a model in one launch (after the optimizer step)."""
-    nt, ne = len(towers), len(embeds)
-    tp = (C.POINTER(L.Tower) * max(nt, 1))(*[C.pointer(t.desc) for t in towers])
-    ep = (C.POINTER(L.Embed) * max(ne, 1))(*[C.pointer(e.desc) for e in embeds])
-    L.check(L.lib().m2m_pack_all(tp, nt, ep, ne, L.stream_ptr()), "pack_all")
+    L.check(L.lib().m2m_pack_all(_tower_ptrs(towers), len(towers), _embed_ptrs(embeds), len(embeds), L.stream_ptr()), "pack_all")
     for t in towers:
         t.mark_packed()
     for e in embeds:
@@ -523,17 +538,14 @@ class AdamPackPlan:
         """ranges: [(lo, n, slot tensor or None, keep), ...] -- the special gradient ranges of m2m_adam_step_ranges."""
         self.towers, self.embeds = list(towers), list(embeds)
         nt, ne = len(towers), len(embeds)
-        self._tp = (C.POINTER(L.Tower) * max(nt, 1))(*[C.pointer(t.desc) for t in towers])
-        self._ep = (C.POINTER(L.Embed) * max(ne, 1))(*[C.pointer(e.desc) for e in embeds])
+        self._tp, self._ep = _tower_ptrs(towers), _embed_ptrs(embeds)
         nbytes = int(L.lib().m2m_adam_pack_plan_bytes())
         self.host = C.create_string_buffer(nbytes)
         ranges = list(ranges or [])
-        arr = (L.GradRange * max(len(ranges), 1))()
-        for i, (rlo, rn, add, keep) in enumerate(ranges):
-            arr[i].lo, arr[i].n, arr[i].add, arr[i].keep = rlo, rn, L.ptr(add), int(keep)
         L.check(L.lib().m2m_adam_pack_plan_ranges(self._tp, nt, self._ep, ne, flat_p.data_ptr(), flat_g.data_ptr(), L.ptr(grad_bf16),
                                                   flat_m.data_ptr(), flat_v.data_ptr(), flat_p.numel(), state.data_ptr(), betas[0], betas[1],
-                                                  eps, weight_decay, abs(grad_scale), arr, len(ranges), self.host), "adam_pack_plan_ranges")
+                                                  eps, weight_decay, abs(grad_scale), _grad_ranges(ranges), len(ranges), self.host),
+                "adam_pack_plan_ranges")
         self.dev = torch.frombuffer(bytearray(self.host.raw), dtype=torch.uint8).to(flat_p.device)
         self._keep = (flat_p, flat_g, grad_bf16, flat_m, flat_v, state, [r[2] for r in ranges])
 
@@ -603,10 +615,7 @@ class EmbedRuntime:
 
     def forward(self, inp: torch.Tensor, B: int, x0: torch.Tensor, step_head: Optional[tuple] = None):
         """step_head = (adam_state, drop_counter, losses): the launch also does the step prologue (m2m_embed_forward_head)."""
-        head = None
-        if step_head is not None:
-            adam_state, drop_counter, losses = step_head
-            head = C.byref(L.StepHead(adam_state.data_ptr(), drop_counter.data_ptr(), losses.data_ptr(), losses.numel()))
+        head = _step_head(step_head[0], step_head[2], step_head[1]) if step_head is not None else None
         L.check(L.lib().m2m_embed_forward_head(C.byref(self.desc), inp.data_ptr(), B, x0.data_ptr(), head, L.stream_ptr()),
                 "embed_forward")
 
@@ -625,25 +634,17 @@ def embeds_forward(embeds: Sequence[EmbedRuntime], inputs: Sequence[torch.Tensor
     receives k-split partial sums (EmbedRuntime.fwd_splits says when that pays off); the consumer adds them.
     step_head = (adam_state, drop_counter, losses): the launch also does the step prologue (m2m_step_prologue)."""
     n = len(embeds)
-    ep = (C.POINTER(L.Embed) * n)(*[C.pointer(e.desc) for e in embeds])
-    ip = (C.c_void_p * n)(*[t.data_ptr() for t in inputs])
-    xp = (C.c_void_p * n)(*[t.data_ptr() for t in x0s])
     ns = (C.c_int * n)(*(nsplits if nsplits is not None else [1] * n))
     ps = (C.c_int64 * n)(*[B * e.N * e.D for e in embeds])
-    head = None
-    if step_head is not None:
-        adam_state, drop_counter, losses = step_head
-        head = C.byref(L.StepHead(adam_state.data_ptr(), drop_counter.data_ptr(), losses.data_ptr(), losses.numel()))
-    L.check(L.lib().m2m_embeds_forward(ep, ip, xp, ns, ps, n, B, head, L.stream_ptr()), "embeds_forward")
+    head = _step_head(step_head[0], step_head[2], step_head[1]) if step_head is not None else None
+    L.check(L.lib().m2m_embeds_forward(_embed_ptrs(embeds), _data_ptrs(inputs), _data_ptrs(x0s), ns, ps, n, B, head, L.stream_ptr()),
+            "embeds_forward")
 
 
 def embeds_wgrad(embeds: Sequence[EmbedRuntime], inputs: Sequence[torch.Tensor], d_x0s: Sequence[torch.Tensor], B: int):
     """Weight / bias gradients of both patch embeddings in one launch."""
-    n = len(embeds)
-    ep = (C.POINTER(L.Embed) * n)(*[C.pointer(e.desc) for e in embeds])
-    ip = (C.c_void_p * n)(*[t.data_ptr() for t in inputs])
-    dp = (C.c_void_p * n)(*[t.data_ptr() for t in d_x0s])
-    L.check(L.lib().m2m_embeds_wgrad(ep, ip, dp, n, B, L.stream_ptr()), "embeds_wgrad")
+    L.check(L.lib().m2m_embeds_wgrad(_embed_ptrs(embeds), _data_ptrs(inputs), _data_ptrs(d_x0s), len(embeds), B, L.stream_ptr()),
+            "embeds_wgrad")
 
 
 class MlpRuntime:
@@ -698,8 +699,7 @@ class MlpRuntime:
         _check_tensor(x, (B, self.dims[0]), "mlp input")
         self.ensure_buffers(B, x.device)
         L.check(L.lib().m2m_mlp_forward(C.byref(self.desc), x.data_ptr(), B, out.data_ptr(), out_ss, L.ptr(out_dense),
-                                        int(training), seed & 0xFFFFFFFF, step & 0xFFFFFFFF, L.ptr(step_dev),
-                                        L.stream_ptr()), "mlp_forward")
+                                        int(training), *_drop_tail(seed, step, step_dev)), "mlp_forward")
 
     def backward(self, x: torch.Tensor, B: int, d_out: Optional[torch.Tensor], d_out_ss: int,
                  d_out_dense: Optional[torch.Tensor]):
@@ -713,7 +713,7 @@ class MlpRuntime:
         _check_tensor(x, (B, self.dims[0]), "mlp input")
         self.ensure_buffers(B, x.device)
         L.check(L.lib().m2m_mlp_forward_ride(C.byref(self.desc), x.data_ptr(), B, out.data_ptr(), out_ss, L.ptr(out_dense),
-                                             int(training), seed & 0xFFFFFFFF, step & 0xFFFFFFFF, L.ptr(step_dev)), "mlp_forward_ride")
+                                             int(training), *_drop_tail(seed, step, step_dev)[:3]), "mlp_forward_ride")
 
     def backward_ride(self, x: torch.Tensor, B: int, d_out: Optional[torch.Tensor], d_out_ss: int,
                       d_out_dense: Optional[torch.Tensor]):

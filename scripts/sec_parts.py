@@ -28,4 +28,4 @@ if task == "mmimdb":
         print("  embed %s alone %.1f us" % (n, timeit(lambda: e.wgrad(x, d, B))))
     print("merged %.1f us" % timeit(lambda: towers_wgrad(tw, B, em, inp, dx)))
     print("pack_all %.1f us" % timeit(lambda: pack_all([eng.t_a, eng.t_b, eng.t_fus], em)))
-print("adam (whole flat buffer) %.1f us" % timeit(lambda: eng._adam(0, eng.n_params, 1.0, False) if hasattr(eng, "n_params") else None))
+print("adam (whole flat buffer) %.1f us" % timeit(lambda: eng._adam(0, eng.n_params, 1.0) if hasattr(eng, "n_params") else None))

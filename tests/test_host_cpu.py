@@ -611,6 +611,7 @@ class _StubEngine:
         self.preds = torch.zeros(3, batch_size, dtype=torch.int32)
         self.exchanges = counter if counter is not None else [0]
         self.packs = 0
+        self._tail_engines = {}
 
     def sibling(self, bs, trains=True):
         return _StubEngine(bs, self.flat_p, self.exchanges)
