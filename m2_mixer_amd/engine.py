@@ -1255,8 +1255,11 @@ class MimicEngine(_FlatEngine):
         # merged tail: the input projection's weight gradient in the towers' weight-gradient launch (one launch less)
         self._embed_wgrad_merged = config.switch_on("M2M_MIMIC_EMBED_WGRAD_MERGED")
         self._conc_fwd, self._conc_bwd = mode in ("fwd", "both"), mode in ("bwd", "both")
-        self._heads_pool = config.switch_on("M2M_HEADS_POOL")       # (both towers are wide: N = 24 / 25)
-        # the static MLP's two launches as extra workgroups of the time tower's token-mixing launches (MlpRuntime.forward_ride)
+        # the heads pool the time and fusion towers' tokens themselves (m2m_head.tokens), on either path: a wide tower (MIMIC-H:
+        # N = 24 / 25) would append a token-mean launch, a fused one (num_patch <= 8 / <= 7) is simply not asked to pool
+        self._heads_pool = config.switch_on("M2M_HEADS_POOL")
+        # the static MLP's two launches as extra workgroups of the time tower's token-mixing launches (MlpRuntime.forward_ride);
+        # a fused time tower has no such launch and ride_flush launches the recorded call on its own
         self._mlp_ride = config.switch_on("M2M_MLP_RIDE") and self.B <= 2048
         self.t_time = self._make_tower("time_mixer.", ct, self.Nt, 0)
         self.t_fus = self._make_tower("fusion_mixer.", cm, self.Nf, 2048)

@@ -1,0 +1,132 @@
+"""Helpers of the engine tests: the float64 reference of an engine step (autograd through the oracle's task forwards +
+oracle.adam_step, in the manner of fusion_ref.Step, with the kernels' dropout masks), the dropout masks and the dispatch
+decisions read off a built engine, and the gradient-clearing check."""
+from collections import OrderedDict
+
+import torch
+
+import gen_util as G
+from oracle import m2mixer_oracle as O
+
+NOISE_KEYS = ("token_mix.2.net.3.bias",)       # rounding-level gradient under a final LayerNorm
+
+
+def p_effective(p):
+    """The keep probability is quantised to 16 bits; the kernels scale by 1 / keep_q."""
+    return 1 - round((1 - p) * 65536) / 65536
+
+
+def grads_cleared(eng):
+    """After an optimizer step every gradient element Adam is responsible for clearing is zero: everything outside the ranges
+    the engine leaves to the next backward's overwriting weight-gradient launch (engine._setup_wgrad)."""
+    g = eng.flat_g.detach().clone()
+    for lo, n, _, keep in eng._ranges_add:
+        if keep:
+            g[lo:lo + n] = 0
+    return float(g.abs().max()) == 0.0
+
+
+def tower_masks(rt, B, seed, step):
+    """The keep-masks of one tower's dropout sites at `step`, per block, in the oracle's layout."""
+    blocks = []
+    for b in range(rt.nblocks):
+        m = {"tok_h": rt.dropout_mask(b, 0, B, seed, step).view(B, rt.D, rt.T),
+             "tok_o": rt.dropout_mask(b, 1, B, seed, step).view(B, rt.D, rt.N),
+             "ch_h": rt.dropout_mask(b, 2, B, seed, step).view(B, rt.N, rt.Cp)[:, :, :rt.C],
+             "ch_o": rt.dropout_mask(b, 3, B, seed, step).view(B, rt.N, rt.D)}
+        blocks.append({k: v.float().cpu() for k, v in m.items()})
+    return blocks
+
+
+def engine_masks(eng, B):
+    """The keep-masks of every dropout site of a two-tower engine's three towers at its current step."""
+    step, seed = int(eng.drop_step[0]), eng.seed
+    return {name: tower_masks(rt, B, seed, step) for name, rt in ((eng.MODS[0], eng.t_a), (eng.MODS[1], eng.t_b), ("fusion", eng.t_fus))}
+
+
+# ---- the case table's engines ------------------------------------------------------------------------------------------------
+HEAD_LOGITS = {"avmnist": ("image_logits", "audio_logits", "logits"), "mmimdb": ("image_logits", "text_logits", "logits"),
+               "mimic": ("logits_static", "logits_time", "logits")}
+HEAD_LOSSES = {"avmnist": ("loss_image", "loss_audio", "loss_fusion", "loss"), "mmimdb": ("loss_image", "loss_text", "loss_fusion", "loss"),
+               "mimic": ("loss_static", "loss_time", "loss_fusion", "loss")}
+
+
+def case_shapes(case) -> "OrderedDict[str, tuple]":
+    return {"avmnist": G.avmnist_shapes, "mmimdb": G.mmimdb_shapes, "mimic": G.mimic_shapes}[case.engine](case.cfg)
+
+
+def case_batch(case, seed):
+    return {"avmnist": G.avmnist_batch, "mmimdb": G.mmimdb_batch, "mimic": G.mimic_batch}[case.engine](case.B, seed, case.cfg)
+
+
+def engine_class(case):
+    from m2_mixer_amd import engine as E
+    return {"avmnist": E.AVMnistEngine, "mmimdb": E.MMIMDBEngine, "mimic": E.MimicEngine}[case.engine]
+
+
+def case_forward(case, batch, p, drop_p=0.0, masks=None):
+    """The task's shared_step in float64: {"logits": (3, B, K) in the engine's head order, "losses": (4,) heads then total}."""
+    x1, x2, y = batch
+    x1, x2 = x1.double(), x2.double()
+    if case.engine == "avmnist":
+        o = O.avmnist_forward(x1, x2, y, p, case.cfg, drop_p, masks)
+    elif case.engine == "mmimdb":
+        o = O.mmimdb_forward(x1, x2, y.double(), p, case.cfg, torch.tensor(case.cfg["pos_weight"], dtype=torch.float64), drop_p, masks)
+    else:
+        o = O.mimic_forward(x1, x2, y, p, case.cfg, drop_p, masks)
+    return {"logits": torch.stack([o[k] for k in HEAD_LOGITS[case.engine]]), "losses": torch.stack([o[k] for k in HEAD_LOSSES[case.engine]])}
+
+
+class Step:
+    """Autograd through case_forward in float64, then torch.optim.Adam's update (oracle.adam_step) of every parameter."""
+
+    def __init__(self, case, params, lr):
+        self.case, self.lr = case, lr
+        self.p = {k: v.detach().double().clone() for k, v in params.items()}
+        self.t, self.m, self.v = 0, {}, {}
+
+    def forward(self, batch, params=None):
+        with torch.no_grad():
+            return case_forward(self.case, batch, self.p if params is None else params)
+
+    def step(self, batch, masks=None):
+        leaves = {k: v.clone().requires_grad_(True) for k, v in self.p.items()}
+        out = case_forward(self.case, batch, leaves, p_effective(self.case.p) if masks is not None else 0.0, masks)
+        out["losses"][3].backward()
+        self.t += 1
+        grads = {}
+        for k, leaf in leaves.items():
+            g = leaf.grad if leaf.grad is not None else torch.zeros_like(leaf)
+            grads[k] = g
+            m, v = self.m.get(k, torch.zeros_like(g)), self.v.get(k, torch.zeros_like(g))
+            self.p[k], self.m[k], self.v[k] = O.adam_step(self.p[k], g, m, v, self.t, self.lr)
+        out = {k: v.detach() for k, v in out.items()}
+        out["grads"] = grads
+        return out
+
+
+def decisions(eng) -> dict:
+    """Every dispatch decision of tests/engine_cases.py as the built engine took it."""
+    from m2_mixer_amd.engine import MimicEngine
+    from m2_mixer_amd.runtime import can_group, can_group_embeds, can_pack_all
+    B = eng.B
+    d = {"heads_pool": bool(eng._heads_pool), "fused_heads": bool(eng._fused_heads),
+         "pack_all": bool(can_pack_all(eng._towers, eng._embeds)), "adam_pack": eng._adam_pack_modules() is not None,
+         "wide_fus": bool(eng.t_fus.wide)}
+    if isinstance(eng, MimicEngine):
+        d.update(time_wide=bool(eng.t_time.wide), mlp_ride=bool(eng._mlp_ride))
+        return d
+    d.update(grouped=bool(can_group(eng.t_a, eng.t_b, B)), embeds_grouped=bool(can_group_embeds(eng.e_a, eng.e_b)),
+             wide_a=bool(eng.t_a.wide), wide_b=bool(eng.t_b.wide), head_part=eng._head_part is not None,
+             embed_fast=bool(eng._embed_towers), embed_overwrite=bool(eng.e_a.desc.wgrad_flags & 1) and bool(eng.e_b.desc.wgrad_flags & 1),
+             group_slots=bool(eng.t_a.desc.wgrad_flags & 4) and bool(eng.t_b.desc.wgrad_flags & 4))
+    for name, t in (("a", eng.t_a), ("b", eng.t_b), ("fus", eng.t_fus)):
+        d["overwrite_" + name] = bool(t.desc.wgrad_flags & 1)
+        d["groups_" + name] = int(t.wgrad_groups(B))
+        d["slot_" + name] = any(t is s for s in eng._slot_towers)
+    return d
+
+
+def expected(case, prec: str) -> dict:
+    """The case's `expect` for one precision."""
+    return {k: (v[prec] if isinstance(v, dict) else v) for k, v in case.expect.items()}

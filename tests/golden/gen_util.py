@@ -188,8 +188,9 @@ def mimic_batch(B: int, seed: int, cfg: dict):
 def mmimdb_batch(B: int, seed: int, cfg: dict):
     rng = np.random.default_rng(seed)
     ih, iw = cfg["image"]["image_size"]
+    th, tw = cfg["text"]["image_size"]           # (the reference's config gives both modalities one size; the engines take any)
     image = torch.from_numpy(rng.standard_normal((B, cfg["image"]["in_channels"], ih, iw)).astype(np.float32))
-    text = torch.from_numpy(rng.standard_normal((B, cfg["text"]["in_channels"], ih, iw)).astype(np.float32))
+    text = torch.from_numpy(rng.standard_normal((B, cfg["text"]["in_channels"], th, tw)).astype(np.float32))
     label = torch.from_numpy((rng.random((B, cfg["num_classes"])) < 0.1).astype(np.float32))
     return image, text, label
 

@@ -15,6 +15,7 @@ import torch
 
 import gen_util as G
 from conftest import observe
+from engine_ref import engine_masks, grads_cleared, p_effective    # (shared with tests/test_gpu_engine_envelope.py)
 from oracle import m2mixer_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -37,39 +38,8 @@ def relerr(a, b):
     return float((a - b).abs().max()) / (float(b.abs().max()) + 1e-12)
 
 
-def grads_cleared(eng):
-    """After an optimizer step every gradient element Adam is responsible for clearing is zero: everything outside the ranges
-    the engine leaves to the next backward's overwriting weight-gradient launch (engine._setup_wgrad)."""
-    g = eng.flat_g.detach().clone()
-    for lo, n, _, keep in eng._ranges_add:
-        if keep:
-            g[lo:lo + n] = 0
-    return float(g.abs().max()) == 0.0
-
-
 def abserr(a, b):
     return float((a.detach().double().cpu() - b.detach().double().cpu()).abs().max())
-
-
-def engine_masks(eng, B):
-    """The keep-masks of every dropout site of the three towers at the engine's current step, in the oracle's layout."""
-    step, seed = int(eng.drop_step[0]), eng.seed
-    out = {}
-    for name, rt in ((eng.MODS[0], eng.t_a), (eng.MODS[1], eng.t_b), ("fusion", eng.t_fus)):
-        blocks = []
-        for b in range(rt.nblocks):
-            m = {"tok_h": rt.dropout_mask(b, 0, B, seed, step).view(B, rt.D, rt.T),
-                 "tok_o": rt.dropout_mask(b, 1, B, seed, step).view(B, rt.D, rt.N),
-                 "ch_h": rt.dropout_mask(b, 2, B, seed, step).view(B, rt.N, rt.Cp)[:, :, :rt.C],
-                 "ch_o": rt.dropout_mask(b, 3, B, seed, step).view(B, rt.N, rt.D)}
-            blocks.append({k: v.float().cpu() for k, v in m.items()})
-        out[name] = blocks
-    return out
-
-
-def p_effective(p):
-    """The keep probability is quantised to 16 bits; the kernels scale by 1 / keep_q."""
-    return 1 - round((1 - p) * 65536) / 65536
 
 
 def assert_preds_match(pred, logits_gpu, logits_ref, tol):
