@@ -10,6 +10,11 @@ void m2m_set_error(const char* msg, const char* file, int line);
 // 0, or -1 with the error set: descriptor fields the kernels are built for (precision, hidden_dim, N, T, blocks, buffers at batch B)
 int m2m_check_tower(const m2m_tower* t, int B);
 
+// (grid and packed-image sizes in api.hip, pack.hip, adam.hip and probes.hip)
+static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// ---- pack.hip, adam.hip, probes.hip: public entry points only (include/m2mixer.h); the packed slot they share: pack.h ----------
+
 // ---- embed.hip -----------------------------------------------------------------------------------------------------------------
 int m2m_check_embed(const m2m_embed* e, int B);
 

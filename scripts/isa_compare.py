@@ -1,4 +1,7 @@
-"""The comparing half of scripts/isa_compare.sh:  isa_compare.py OUT a.hip b.hip ...  reads OUT/a/<stem>.s and OUT/b/<stem>.s."""
+"""The comparing half of scripts/isa_compare.sh:  isa_compare.py OUT a.hip b.hip ...  reads OUT/a/<stem>.s and OUT/b/<stem>.s.
+An argument  a.hip=b.hip+c.hip  compares a file that tree B has split: the B side is the union of OUT/b/b.s and OUT/b/c.s.
+Kernels are compared as ever; data objects and the remaining lines follow the sections of a file, so for a split file their
+differences are printed and do not fail the run."""
 import re
 import sys
 
@@ -82,27 +85,45 @@ def parse(path):
 
 
 PART = ('instructions', 'descriptor', 'metadata')
+USE = re.compile(r'\.(vgpr_count|sgpr_count|vgpr_spill_count|sgpr_spill_count|group_segment_fixed_size|private_segment_fixed_size):\s*(\d+)')
+
+
+def resources(parts):
+    """What a kernel uses, for the report of one that differs: instruction count + the register / spill / LDS / scratch metadata."""
+    use = {'instructions': sum(1 for l in parts[0] if not l.endswith(':') and not l.startswith('.'))}
+    use.update((m.group(1), int(m.group(2))) for m in map(USE.search, parts[2]) if m)
+    return use
+
+
 out, srcs = sys.argv[1], sys.argv[2:]
 bad, total = 0, [0, 0]
 for src in srcs:
-    stem = src[:-4]
-    fa, ka, da, oa = parse(f'{out}/a/{stem}.s')
-    fb, kb, db, ob = parse(f'{out}/b/{stem}.s')
-    diffs = []
+    src, _, split = src.partition('=')
+    fa, ka, da, oa = parse(f'{out}/a/{src[:-4]}.s')
+    fb, kb, db, ob = {}, set(), {}, []
+    for part in (split or src).split('+'):
+        f, k, d, o = parse(f'{out}/b/{part[:-4]}.s')
+        fb.update(f), kb.update(k), db.update(d), ob.extend(o)
+    diffs, soft = [], []
     for name in sorted(set(fa) | set(fb)):
         if name not in fa or name not in fb:
             diffs.append(f'{name} (only in {"A" if name in fa else "B"})')
             continue
-        diffs += [f'{name} ({part})' for i, part in enumerate(PART) if fa[name][i] != fb[name][i]]
-    diffs += [f'{name} (data object)' for name in sorted(set(da) | set(db)) if da.get(name) != db.get(name)]
+        which = [part for i, part in enumerate(PART) if fa[name][i] != fb[name][i]]
+        if which:
+            ra, rb = resources(fa[name]), resources(fb[name])
+            diffs.append(f'{name} ({", ".join(which)}): ' + ', '.join(f'{k} {ra[k]} -> {rb.get(k)}' for k in ra))
+    (soft if split else diffs).extend(f'{name} (data object)' for name in sorted(set(da) | set(db)) if da.get(name) != db.get(name))
     if oa != ob:
-        diffs.append('<other>')
+        (soft if split else diffs).append('<other>')
     total[0] += len(ka)
     total[1] += len(kb)
     print(f'{src:18s} kernels {len(ka):4d} / {len(kb):4d}  other functions {len(fa) - len(ka):2d} / {len(fb) - len(kb):2d}  '
           + ('identical' if not diffs else f'{len(diffs)} differences'))
     for d in diffs:
         print(f'    differs: {d}')
+    for d in soft:
+        print(f'    differs (split file, not counted): {d}')
     bad += bool(diffs)
 print(f'{"total":18s} kernels {total[0]:4d} / {total[1]:4d}  ' + ('identical' if not bad else f'{bad} file(s) differ'))
 sys.exit(1 if bad else 0)

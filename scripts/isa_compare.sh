@@ -2,13 +2,15 @@
 # Device assembly of two source trees, kernel by kernel: the proof that a refactor
 # left the shipped device code alone. Runs without a GPU.
 #
-#   bash scripts/isa_compare.sh [-o OUT] [-j N] [-f "a.hip b.hip"] TREE_A TREE_B [extra hipcc flags]
+#   bash scripts/isa_compare.sh [-o OUT] [-j N] [-f "a.hip b.hip"] [-m "a.hip=a.hip+b.hip"] TREE_A TREE_B [extra hipcc flags]
 #
 # Compiles every source in SRCS of each tree's m2_mixer_amd/csrc/Makefile (or those given
 # with -f) with that Makefile's CXXFLAGS, the extra flags and `--offload-device-only -S`,
 # into OUT/a and OUT/b (default: a fresh temporary directory; an assembly file newer than
 # its source and every header is reused).  Prints, per file, the kernel count of each tree and
-# "identical" or "differs: <kernel>".
+# "identical" or "differs: <kernel>" with what the kernel uses in each tree (instructions, registers, spills, LDS, scratch).
+# -m: TREE_B has split a.hip into the files named; they are compiled in its place and compared as their union, where data objects
+# and "<other>" lines (which follow a file's sections) are printed without failing the run.
 #
 # Compared per function: the symbol name; the instruction text with `;` comments stripped
 # and the function index of local labels (.LBB<n>_<m>, .Lfunc_end<n>) dropped; for kernels
@@ -20,12 +22,13 @@
 # Exit status: 0 all identical, 1 something differs, 2 usage or a failed compile.
 set -u -o pipefail
 usage() { sed -n '5p' "$0" | cut -c3-; exit 2; }
-out=""; jobs=4; only=""
-while getopts "o:j:f:" opt; do
+out=""; jobs=4; only=""; map=""
+while getopts "o:j:f:m:" opt; do
   case $opt in
     o) out=$OPTARG ;;
     j) jobs=$OPTARG ;;
     f) only=$OPTARG ;;
+    m) map=$OPTARG ;;
     *) usage ;;
   esac
 done
@@ -42,11 +45,13 @@ export HIPCC=${HIPCC:-/opt/rocm/bin/hipcc}
 
 mkvar() { sed -n "s/^$2 := //p" "$1/m2_mixer_amd/csrc/Makefile" | head -1; }
 srcs=${only:-$(mkvar "$tree_a" SRCS)}
+pairs=$(for s in $srcs; do [ "$s" = "${map%%=*}" ] && echo "$map" || echo "$s"; done)       # a.hip, or a.hip=its successors in TREE_B
+srcs_b=$(for s in $pairs; do echo "${s#*=}" | tr '+' ' '; done)
 
 todo() {  # one "size, directory, source, assembly file, flags" line per assembly file that is missing or stale
   local side=$1 csrc=$2/m2_mixer_amd/csrc flags s asm
   flags="$(mkvar "$2" CXXFLAGS | sed 's/\$(ARCH)/gfx950/') $extra"
-  for s in $srcs; do
+  for s in $3; do
     asm=$out/$side/${s%.hip}.s
     [ -s "$asm" ] && [ -z "$(find "$csrc" -maxdepth 1 \( -name "$s" -o -name '*.h' \) -newer "$asm")" ] && continue
     rm -f "$asm"
@@ -54,10 +59,10 @@ todo() {  # one "size, directory, source, assembly file, flags" line per assembl
   done
 }
 # (largest translation units first, so that the pool drains evenly)
-{ todo a "$tree_a"; todo b "$tree_b"; } | sort -rn | cut -f2- | xargs -r -d '\n' -P "$jobs" -n 1 bash -c '
+{ todo a "$tree_a" "$srcs"; todo b "$tree_b" "$srcs_b"; } | sort -rn | cut -f2- | xargs -r -d '\n' -P "$jobs" -n 1 bash -c '
   IFS="	" read -r csrc s asm flags <<< "$0"
   cd "$csrc" && $HIPCC $flags --offload-device-only -S -o "$asm.tmp" "$s" 2> "$asm.log" && mv "$asm.tmp" "$asm" ||
     { echo "compile failed: $csrc/$s (see $asm.log)" >&2; exit 255; }
 ' || exit 2
 
-exec python3 "$(dirname "$0")/isa_compare.py" "$out" $srcs
+exec python3 "$(dirname "$0")/isa_compare.py" "$out" $pairs

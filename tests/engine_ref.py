@@ -26,6 +26,23 @@ def grads_cleared(eng):
     return float(g.abs().max()) == 0.0
 
 
+def assert_update_forms_bit_identical(sep, fus):
+    """A two-tower engine that updates with the flat Adam followed by m2m_pack_all (sep) against one that updates with the
+    one-launch m2m_adam_pack_all (fus), after the same steps from the same state: parameters, both moments, the cleared
+    gradient and every packed operand copy the kernels read, BIT FOR BIT."""
+    assert fus._fused_update and not sep._fused_update
+    assert torch.equal(sep.flat_p, fus.flat_p) and torch.equal(sep.flat_m, fus.flat_m) and torch.equal(sep.flat_v, fus.flat_v)
+    assert torch.equal(sep.flat_g, fus.flat_g)
+    for ts, tf in zip((sep.t_a, sep.t_b, sep.t_fus), (fus.t_a, fus.t_b, fus.t_fus)):
+        for i in range(ts.nblocks):
+            for k, v in ts._keep[f"packed{i}"].items():
+                if k == "w1tc" and ts.pack_all_skips_w1tc():
+                    continue
+                assert torch.equal(v, tf._keep[f"packed{i}"][k]), (i, k)
+    for es, ef in zip((sep.e_a, sep.e_b), (fus.e_a, fus.e_b)):
+        assert torch.equal(es._keep["wn"], ef._keep["wn"])
+
+
 def tower_masks(rt, B, seed, step):
     """The keep-masks of one tower's dropout sites at `step`, per block, in the oracle's layout."""
     blocks = []

@@ -1,6 +1,7 @@
 """m2m_adam_step, m2m_adam_step_bf16 and m2m_adam_step_ranges called directly (-m gpu), against float64 Adam on the same
-inputs (tests/leaf_ref.py, pinned to torch.optim.Adam in float64), and one engine-level run of both update forms with
-weight_decay != 0 and non-default betas / eps.
+inputs (tests/leaf_ref.py, pinned to torch.optim.Adam in float64), one engine-level run of both update forms with
+weight_decay != 0 and non-default betas / eps, and the one-launch update (m2m_adam_pack_all) held bit for bit to the flat Adam +
+m2m_pack_all in the builds tests/test_gpu_bench_path.py does not reach (hidden_dim 32 / 64 / 256, fp32, both tile forms).
 
 Bars.  For each tensor (param, exp_avg, exp_avg_sq) two errors are taken against float64 on the same inputs, each relative to the
 tensor's max: the kernel's, and that of torch.optim.Adam on float32 CPU tensors.  The kernel is held to
@@ -275,3 +276,56 @@ def test_engine_update_with_weight_decay_vs_oracle(fused_update, dev, monkeypatc
                 err = float((eng.params[k].cpu() - params[k])[sel].abs().max())
                 assert observe("adam engine wd params (abs)", err, 3e-4) < 3e-4, (step, k, err)
     assert sum(int(v.sum()) for v in significant.values()) > 0.3 * eng.n_params
+
+
+# (engine, hidden_dim, channel_dim, precision, M2M_AP_ROWTILES or None: the tower is too narrow for row tiles either way).
+# The one-launch update is compiled once per hidden_dim every tower of the launch shares (64, 128, 256) plus once for any other
+# (32); tests/test_gpu_bench_path.py holds the 128 / bf16 build to this check, these are the others at their smallest shapes.
+# channel_dim 33 -> Cp 64: one full and one ragged 32-column group (the float4 path and the element tail); 518 -> Cp 544: past the
+# 512-column chunk of the row-tile form (bf16 only), one full and one ragged chunk.
+UPDATE_FORMS = [("avmnist", 32, 33, "fp32", None), ("avmnist", 32, 33, "bf16", None),
+                ("avmnist", 64, 33, "fp32", None), ("avmnist", 64, 33, "bf16", None),
+                ("mmimdb", 256, 33, "fp32", None), ("mmimdb", 256, 33, "bf16", None),
+                ("avmnist", 64, 518, "bf16", "1"), ("avmnist", 64, 518, "bf16", "0"),
+                ("mmimdb", 256, 518, "bf16", "1"), ("mmimdb", 256, 518, "bf16", "0")]
+
+
+@pytest.mark.parametrize("engine,D,C,prec,rowtiles", UPDATE_FORMS,
+                         ids=[f"{e}-d{D}-c{C}-{p}" + ("" if r is None else f"-rowtiles{r}") for e, D, C, p, r in UPDATE_FORMS])
+def test_one_launch_update_is_bit_identical_to_adam_then_repack(engine, D, C, prec, rowtiles, dev, monkeypatch):
+    """Two training steps with the one-launch Adam + re-pack (M2M_FUSED_UPDATE=1) against the flat Adam followed by
+    m2m_pack_all (0) on engines loaded with the same state: one block per tower, images (8, 8) and (16, 16), batch 5.  Same
+    arithmetic per element, so everything the update writes must agree bit for bit.  The reference side is the flat Adam,
+    which the tests above hold to float64.
+
+    Both updates of a step consume the SAME gradient: the one-launch engine's backward runs, then its flat gradient is
+    overwritten with the two-launch engine's.  At these shapes the small gradients (LayerNorms, token mixing, biases, heads, in
+    fp32 the embeddings) are summed with float atomics, so two engines in the SAME update form already differ in the last bits
+    after two steps (measured on every case here); without the copy the test would compare backward runs, not update forms.
+    No range of these engines has a slot to add (asserted), so the flat gradient is everything the update reads."""
+    import engine_cases as EC
+    import engine_ref as ER
+    make = EC._av if engine == "avmnist" else EC._mm
+    case = make(f"update_{engine}_d{D}_c{C}", EC._tower(D, (8, 8), 4, C=C), EC._tower(D, (16, 16), 8, C=C), EC._fusion(D, C=C), B=5)
+    params = G.make_params(ER.case_shapes(case), 31)
+    batch = tuple(t.to(dev) for t in ER.case_batch(case, 101))
+    if rowtiles is not None:
+        monkeypatch.setenv("M2M_AP_ROWTILES", rowtiles)
+    engs = []
+    for fused in ("0", "1"):
+        monkeypatch.setenv("M2M_FUSED_UPDATE", fused)
+        e = ER.engine_class(case)(case.cfg, case.B, device=dev, precision=prec, lr=LR, init=False)
+        e.load_state_dict(params)
+        engs.append(e)
+    sep, fus = engs
+    assert fus._adam_pack_modules() is not None
+    assert all(add is None for e in engs for _, _, add, _ in e._ranges_add)
+    for _ in range(2):
+        for e in engs:
+            e.forward_backward(*batch)
+        fus.flat_g.copy_(sep.flat_g)
+        for e in engs:
+            e.optimizer_step()
+    torch.cuda.synchronize()
+    assert float(sep.adam_state[0]) == 2.0 and float(fus.adam_state[0]) == 2.0
+    ER.assert_update_forms_bit_identical(sep, fus)

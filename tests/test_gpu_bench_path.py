@@ -15,7 +15,7 @@ import torch
 
 import gen_util as G
 from conftest import observe
-from engine_ref import engine_masks, grads_cleared, p_effective    # (shared with tests/test_gpu_engine_envelope.py)
+from engine_ref import assert_update_forms_bit_identical, engine_masks, grads_cleared, p_effective    # (shared with the other engine tests)
 from oracle import m2mixer_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -191,16 +191,7 @@ def test_one_launch_update_is_bit_identical_to_adam_then_repack_bf16(rowtiles, d
         for e in engs:
             e.train_step(*batch)
     torch.cuda.synchronize()
-    assert torch.equal(sep.flat_p, fus.flat_p) and torch.equal(sep.flat_m, fus.flat_m) and torch.equal(sep.flat_v, fus.flat_v)
-    assert torch.equal(sep.flat_g, fus.flat_g)
-    for ts, tf in zip((sep.t_a, sep.t_b, sep.t_fus), (fus.t_a, fus.t_b, fus.t_fus)):
-        for i in range(ts.nblocks):
-            for k, v in ts._keep[f"packed{i}"].items():
-                if k == "w1tc" and ts.pack_all_skips_w1tc():
-                    continue
-                assert torch.equal(v, tf._keep[f"packed{i}"][k]), (i, k)
-    for es, ef in zip((sep.e_a, sep.e_b), (fus.e_a, fus.e_b)):
-        assert torch.equal(es._keep["wn"], ef._keep["wn"])
+    assert_update_forms_bit_identical(sep, fus)
 
 
 def test_update_from_a_bf16_gradient_copy_agrees_in_all_three_forms(dev, monkeypatch):
