@@ -97,14 +97,16 @@ typedef struct m2m_tower {
      * a per-sample launch (token mixing, LayerNorms, residual) and a channel-mixing launch whose workgroups own 128 token
      * rows x 1/nsplit of the hidden columns, so each CU streams 1/nsplit of the weights for 8x the rows.  Results are the
      * same up to fp32 summation order.  slabs == NULL (or nsplit < 2) keeps the one-launch-per-tower path. */
-    float* slabs;          /* nsplit x (B*N, D) fp32: partial results of the column-split launches                       */
+    float* slabs;          /* nsplit x (ceil(B / (16 / N)) * 16, D) fp32: partial results of the column-split launches, 16 rows per
+                            * 16-row tile of whole samples (= B*N rows when N divides 16 and 16 divides B*N)                  */
     int32_t nsplit;        /* slabs the buffer has room for (the library uses up to 8)                                     */
     int32_t wgrad_flags;   /* M2M_WGRAD_* (weight-gradient launches)                                                        */
     float* xres;           /* (B*N, D) fp32: residual / gradient stream carried between the launches                       */
     float* gpart;          /* (nblocks + 1 [+ 3: m2m_tower_backward_heads]) x ceil(B / (16 / N)) x M2M_SPLIT_GPART floats: per-workgroup partial sums of the small
                             * gradients (LayerNorms, token MLP, ch_b2), stored plainly and summed by one reduction launch --
                             * deterministic, and free of the same-address atomics of 256 workgroups                          */
-    void* a_nat[M2M_MAX_BLOCKS];   /* per block: LN2(x_mid) as packed NAT blocks [16-row tile][k-block], rows padded to 16 */
+    void* a_nat[M2M_MAX_BLOCKS];   /* per block: LN2(x_mid) as packed NAT blocks [16-row tile][k-block]: ceil(B / (16 / N)) tiles of
+                                    * whole samples, each padded to 16 rows                                                 */
     void* dy_nat[M2M_MAX_BLOCKS];  /* per block: d(channel MLP out) after its dropout mask, same layout                    */
     /* ---- weight-gradient slot (optional) ---------------------------------------------------------------------------------
      * per block 2 C D + C floats laid out [dW1 (C, D) | db1 (C) | dW2 (D, C)] (NULL: none).  With it -- and g_ch_w1 / g_ch_b1 /
@@ -264,6 +266,11 @@ int m2m_towers_backward(const m2m_tower* const* towers, const m2m_tower_gio* io,
  *      backward left in h_chn and streams only dHpre^T; needs the dropout stream: seed / step / step_dev as in the forward. */
 int m2m_tower_wgrad(const m2m_tower* t, int B, uint32_t seed, uint32_t step, const uint32_t* step_dev, void* stream);
 int m2m_wgrad_form(const m2m_tower* t, int B);
+/* Which path a tower call takes (additive within ABI 18; launches nothing): the number of column splits S (2..8) that
+ * m2m_tower_forward / _backward use for `a` at batch B when b is NULL, or m2m_towers_forward / _backward for the pair (a, b) --
+ * both towers take the column-split path (M2M_SPLIT / M2M_SPLIT_MIN_ROWS, csrc/split.h) with the same mix instantiation, depth and
+ * split count -- and 0 when the call takes the fused or the wide launch.  training as in m2m_tower_forward (the backward: 1). */
+int m2m_split_form(const m2m_tower* a, const m2m_tower* b, int B, int training);
 /* The same for up to 4 towers (same precision and hidden_dim) in ONE launch: the towers of a model finish their backward
  * chains together, and one launch lets the hardware balance all their workgroups over the chip.  `dev_towers[i]` is a
  * device-resident byte copy of *towers[i] (kernel arguments are limited to 4 KiB; the caller refreshes the copy whenever

@@ -155,6 +155,7 @@ SIGNATURES = {
                                         C.POINTER(Head), C.c_int, C.c_int, _fp, _fp]),
     "m2m_heads_part_tiles": (C.c_int, [C.c_int]),
     "m2m_wgrad_form": (C.c_int, [C.POINTER(Tower), C.c_int]),
+    "m2m_split_form": (C.c_int, [C.POINTER(Tower), C.POINTER(Tower), C.c_int, C.c_int]),
     "m2m_embeds_wgrad_form": (C.c_int, [C.POINTER(C.POINTER(Embed)), C.POINTER(C.POINTER(Tower)), C.c_int, C.c_int]),
     "m2m_wgrad_groups": (C.c_int, [C.POINTER(Tower), C.c_int]),
     "m2m_wgrad_slot_groups": (C.c_int, [C.POINTER(C.POINTER(Tower)), C.c_int, C.c_int]),

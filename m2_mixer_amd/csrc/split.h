@@ -34,7 +34,10 @@ struct SplitChainTower {
     const float* b1p;
     float* slabs;                 // [nsplit][M][D] fp32 partial results
     char* h_chn; char* dh_chn;    // backward: operand streams of the weight-gradient launch (layout: tower_bwd.hip)
-    int M;                        // token rows
+    int M;                        // rows of the operand images: 16 per mix workgroup (ceil(B / (16 / N)) * 16), of which the
+                                  // first `rpt` of every 16 are token rows -- the row space of the images, the slabs and the
+                                  // weight-gradient streams; B * N only when N divides 16
+    int rpt;                      // token rows per 16-row tile: (16 / N) * N
     int nunits;                   // Cp / 32
     int Cp;
     unsigned int site;            // dropout site of the channel-hidden activation of this block
@@ -50,7 +53,7 @@ struct SplitMixTower {
     // ---- input of the residual stream ----
     const float* x0; long x0_ss; int x0_parts; long x0_pstride;      // first block: the tower input (sum of x0_parts buffers)
     const float* xprev;           // later: x_mid of the previous block ...
-    const float* slabs; int nslab; long slab_stride;                  // ... + dropout(sum of the slabs + b2prev)
+    const float* slabs; int nslab; long slab_stride;                  // ... + dropout(sum of the slabs + b2prev); slab rows: 16 per workgroup
     const float* b2prev;
     unsigned int site_prev_out;   // dropout site (channel output) of the previous block
     // ---- this block (NULL ln1_w: no block, only the final LayerNorm) ----

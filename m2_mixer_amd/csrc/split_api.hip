@@ -1,5 +1,5 @@
 // Host side of the split path: decides when a tower takes it and issues its launch sequence (see split.h).  Entered from
-// m2m_tower(s)_forward / _backward; nothing here is a new C-ABI entry point.
+// m2m_tower(s)_forward / _backward; the one C-ABI entry point here is the query m2m_split_form.
 #include "host.h"
 
 // Rows (B * N) from which the split path pays: below it the chain launches cannot fill the chip (one workgroup per 128 rows
@@ -43,11 +43,23 @@ static void chain_tower(SplitChainTower& c, const m2m_tower* t, int b, int B) {
     c.b1p = k.ch_b1p;
     c.slabs = t->slabs;
     c.h_chn = (char*)k.h_chn; c.dh_chn = (char*)k.dh_chn;
-    c.M = B * t->N;
+    // rows as the mix launches lay them out: 16 per workgroup, whole samples -- with N = 3, 5, 6 or 7 a tile holds 15, 15, 12 or
+    // 14 token rows and the images, the slabs and the weight-gradient streams have more rows than B * N
+    const int SPW = BM / t->N;
+    c.M = (B + SPW - 1) / SPW * BM;
+    c.rpt = SPW * t->N;
     c.nunits = t->Cp / 32;
     c.Cp = t->Cp;
     c.site = t->site_base + 4u * b + 2u;
     c.p_drop = t->p_drop;
+}
+
+// The split count the call would use (include/m2mixer.h): the decision of m2m_tower(s)_forward / _backward, and nothing launched.
+extern "C" int m2m_split_form(const m2m_tower* a, const m2m_tower* b, int B, int training) {
+    if (!a || m2m_check_tower(a, B) != 0 || (b && m2m_check_tower(b, B) != 0)) return 0;
+    if (!m2m_split_eligible(a, B, training)) return 0;
+    if (b && (!m2m_split_eligible(b, B, training) || !m2m_split_can_group(a, b))) return 0;
+    return split_count(a);
 }
 
 // Forward of `ntow` (1 or 2) towers of equal depth: per block a mix launch and a chain launch, then the final mix launch.
@@ -62,7 +74,6 @@ int m2m_split_forward(const m2m_tower* const* towers, const m2m_tower_io* io, in
         for (int i = 0; i < ntow; ++i) {
             const m2m_tower* t = towers[i];
             SplitMixTower& x = m.t[i];
-            const long M = (long)B * t->N;
             x.N = t->N; x.T = t->T; x.B = B; x.p_drop = t->p_drop;
             const int SPW = BM / t->N;
             x.ntiles = (B + SPW - 1) / SPW;
@@ -72,7 +83,7 @@ int m2m_split_forward(const m2m_tower* const* towers, const m2m_tower_io* io, in
                 x.x0_pstride = (long)io[i].x0_part_stride;
             } else {
                 x.xprev = training ? t->blk[b - 1].x_mid : t->xres;
-                x.slabs = t->slabs; x.nslab = S; x.slab_stride = M * t->D;
+                x.slabs = t->slabs; x.nslab = S; x.slab_stride = (long)x.ntiles * BM * t->D;
                 x.b2prev = t->blk[b - 1].ch_b2;
                 x.site_prev_out = t->site_base + 4u * (b - 1) + 3u;
             }
@@ -119,7 +130,6 @@ int m2m_split_backward(const m2m_tower* const* towers, const m2m_tower_gio* io, 
         for (int i = 0; i < ntow; ++i) {
             const m2m_tower* t = towers[i];
             SplitMixBwdTower& x = m.t[i];
-            const long M = (long)B * t->N;
             x.N = t->N; x.T = t->T; x.B = B; x.p_drop = t->p_drop;
             const int SPW = BM / t->N;
             x.ntiles = (B + SPW - 1) / SPW;
@@ -133,7 +143,7 @@ int m2m_split_backward(const m2m_tower* const* towers, const m2m_tower_gio* io, 
                 x.has_upper = 1;
                 x.up = t->blk[upper];
                 x.site_up = t->site_base + 4u * upper;
-                x.slabs = t->slabs; x.nslab = S; x.slab_stride = M * t->D;
+                x.slabs = t->slabs; x.nslab = S; x.slab_stride = (long)x.ntiles * BM * t->D;
             }
             if (lower >= 0) {
                 x.has_lower = 1;

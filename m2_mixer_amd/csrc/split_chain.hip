@@ -167,7 +167,7 @@ __global__ __launch_bounds__(SP_THREADS, 2) void split_chain_fwd_kernel(const Sp
             Frag hf[2];
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
-                const unsigned int m = row_base + 16 * mt + il;
+                const unsigned int m = (row_base / 16 + mt) * (unsigned int)tw.rpt + il;      // token row of image row 16 tile + il
                 const unsigned int word = drop_hidden_bits<DM>(dr, m, (unsigned int)unit, (unsigned int)tw.Cp) >> (4 * g);
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
@@ -355,7 +355,7 @@ __global__ __launch_bounds__(SP_THREADS, 2) void split_chain_bwd_kernel(const Sp
             Frag hf[2], af[2];
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
-                const unsigned int m = row_base + 16 * mt + il;
+                const unsigned int m = (row_base / 16 + mt) * (unsigned int)tw.rpt + il;      // token row of image row 16 tile + il
                 const unsigned int word = drop_hidden_bits<DM>(dr, m, (unsigned int)unit, (unsigned int)tw.Cp) >> (4 * g);
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {

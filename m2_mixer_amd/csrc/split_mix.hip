@@ -77,14 +77,14 @@ __global__ __launch_bounds__(NTHREADS) void split_mix_fwd_kernel(const SplitMixA
             const int r = idx / (D / 4), c = (idx % (D / 4)) * 4;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (r < R) {
-                const long off = (row0 + r) * D + c;
+                const long off = (row0 + r) * D + c, soff = ((long)wg * BM + r) * D + c;      // (slab rows: 16 per workgroup)
                 float4 y = *reinterpret_cast<const float4*>(tw.b2prev + c);
                 // all slab loads in flight together (a runtime-length loop issues them one L2 round trip after another);
                 // slots past nslab re-read the last slab and are discarded
                 float4 u[SP_MAX_SPLITS];
 #pragma unroll
                 for (int s = 0; s < SP_MAX_SPLITS; ++s)
-                    u[s] = *reinterpret_cast<const float4*>(tw.slabs + (long)min(s, tw.nslab - 1) * tw.slab_stride + off);
+                    u[s] = *reinterpret_cast<const float4*>(tw.slabs + (long)min(s, tw.nslab - 1) * tw.slab_stride + soff);
 #pragma unroll
                 for (int s = 0; s < SP_MAX_SPLITS; ++s) {
                     const float k = s < tw.nslab ? 1.f : 0.f;
@@ -298,12 +298,12 @@ __global__ __launch_bounds__(NTHREADS) void split_mix_bwd_kernel(const SplitMixB
             const int r = idx / (D / 4), c = (idx % (D / 4)) * 4;
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f), y = v;
             if (r < R) {
-                const long off = (row0 + r) * D + c;
+                const long off = (row0 + r) * D + c, soff = ((long)wg * BM + r) * D + c;      // (slab rows: 16 per workgroup)
                 v = *reinterpret_cast<const float4*>(tw.carry + off);
                 float4 u[SP_MAX_SPLITS];
 #pragma unroll
                 for (int s = 0; s < SP_MAX_SPLITS; ++s)
-                    u[s] = *reinterpret_cast<const float4*>(tw.slabs + (long)min(s, tw.nslab - 1) * tw.slab_stride + off);
+                    u[s] = *reinterpret_cast<const float4*>(tw.slabs + (long)min(s, tw.nslab - 1) * tw.slab_stride + soff);
 #pragma unroll
                 for (int s = 0; s < SP_MAX_SPLITS; ++s) {
                     const float k = s < tw.nslab ? 1.f : 0.f;

@@ -242,10 +242,11 @@ class TowerRuntime:
         if self.wide or self.prec != L.PREC_BF16 or self.D != 128 or self.nblocks == 0 or B == self._splitB:
             return
         M = B * self.N
-        ntile16 = (M + 15) // 16
-        img = ntile16 * (self.D // 32) * 1024
+        # the mix launches' 16-row tiles hold whole samples: the operand images and the slabs have 16 rows per tile, which is
+        # more than B * N rows when N does not divide 16
         ntiles = (B + (16 // self.N) - 1) // (16 // self.N)
-        bufs = {"slabs": torch.empty(L.SPLIT_MAX, M, self.D, device=self.device), "xres": torch.empty(M, self.D, device=self.device),
+        img = ntiles * (self.D // 32) * 1024
+        bufs = {"slabs": torch.empty(L.SPLIT_MAX, ntiles * 16, self.D, device=self.device), "xres": torch.empty(M, self.D, device=self.device),
                 # (+ 3 slot sets: the classification heads of m2m_tower_backward_heads)
                 "gpart": torch.zeros((self.nblocks + 4) * ntiles * L.SPLIT_GPART, device=self.device),
                 "a_nat": [torch.zeros(img, dtype=torch.uint8, device=self.device) for _ in range(self.nblocks)],
@@ -332,6 +333,11 @@ class TowerRuntime:
     def wgrad_form(self, B: int) -> int:
         """1: the library's weight-gradient launch recomputes the hidden activation for this tower at batch B."""
         return int(L.lib().m2m_wgrad_form(C.byref(self.desc), B))
+
+    def split_form(self, B: int, training: bool = True, other: Optional["TowerRuntime"] = None) -> int:
+        """Column splits this tower's forward / backward uses at batch B (alone, or launched as a pair with `other`); 0: the
+        fused or the wide launch.  Asks the library (m2m_split_form); launches nothing, but needs the buffers of ensure_workspace."""
+        return int(L.lib().m2m_split_form(C.byref(self.desc), C.byref(other.desc) if other is not None else None, B, int(training)))
 
     def wgrad_groups(self, B: int) -> int:
         return int(L.lib().m2m_wgrad_groups(C.byref(self.desc), B))
