@@ -524,6 +524,38 @@ int m2m_gate_wgrad(const m2m_gate* g, const float* a, const float* b, int64_t ro
 int m2m_scores_multiclass(const int32_t* preds, const int64_t* labels, int nheads, int B, int K, uint64_t* table, void* stream);
 int m2m_scores_multilabel(const int32_t* preds, const float* targets, int nheads, int B, int K, uint64_t* table, void* stream);
 
+/* ---- ranking buffers: average precision and ROC-AUC (additive within ABI 18; csrc/rank.hip) -----------------------------------
+ * The reference's MIMIC module ranks the softmax of its heads' logits (models/mimic.py:126-128) with
+ * torchmetrics.AveragePrecision(task="multiclass", average="macro"), which it calls `auroc` (models/mimic.py:162-180).  Average
+ * precision and ROC-AUC are functions of four integers per sample: for a sample i of class c with score s_i = p_i[c], n_ge / p_ge
+ * = the number of samples / of class-c samples whose class-c score is >= s_i, n_gt / p_gt the same with >.  A step appends its
+ * batch's softmax rows to a device buffer; one O(n^2) launch per epoch end produces the integers; the derived numbers are host
+ * arithmetic (m2_mixer_amd/scores.py).  Integer atomics only, no sort: exact and independent of the order of execution.
+ *
+ * Layout: probs[h][c][row] float -- row stride 1, class stride `capacity`, head stride K * capacity; row_labels[row] int32.
+ * state: M2M_RANK_STATE_WORDS uint32 the caller clears (e.g. hipMemsetAsync) at an epoch start:
+ *   [0] rows appended so far (keeps counting past capacity: an overflow is visible to the host; 32 bits)
+ *   [1] arrival ticket of the workgroups of one append (zero between launches)
+ *   [2] appended rows whose label was outside [0, K) (counted past capacity too)
+ *   [3] reserved
+ *
+ *   m2m_rank_append  logits (nheads, B, K) and labels (B) int64, as m2m_heads_ce holds them.  Reads the base row r0 = state[0] on
+ *                    the device (a replayed graph has no host cursor), stores the fp32 softmax of every row of every head
+ *                    (maximum subtracted, expf, the sum in index order, one division per element) at rows r0 .. r0 + B - 1 and
+ *                    the label as int32 (-1 where it lies outside [0, K)); rows at or past `capacity` are not written; the last
+ *                    workgroup to arrive adds B to state[0].  B >= 1.
+ *   m2m_rank_counts  for every head h and row i < n with y = row_labels[i] in [0, K): counts[h][i] = {n_ge, p_ge, n_gt, p_gt}
+ *                    over the rows j < n with a label in [0, K), comparing probs[h][y][j] with probs[h][y][i] (row i counts itself
+ *                    in the >= counts; p_* counts the rows with row_labels[j] == y; a NaN compares false).  Rows without such a
+ *                    label get four zeros and are invisible to the others.  counts (nheads, n, 4) uint32, 16-byte aligned;
+ *                    0 <= n <= capacity, n < 2^31 (n = 0: no launch).
+ * K <= M2M_SCORES_MAX_CLASSES; capacity >= 1; no NULL pointers. */
+#define M2M_RANK_STATE_WORDS 4
+int m2m_rank_append(const float* logits, const int64_t* labels, int nheads, int B, int K, float* probs, int32_t* row_labels,
+                    int64_t capacity, uint32_t* state, void* stream);
+int m2m_rank_counts(const float* probs, const int32_t* row_labels, int nheads, int64_t n, int K, int64_t capacity, uint32_t* counts,
+                    void* stream);
+
 /* ---- test hooks ----------------------------------------------------------------------------------- */
 /* keep-mask (uint8, 1 keep) the kernels use for dropout site `site` (0 tok hidden, 1 tok out,
  * 2 channel hidden, 3 channel out) of block `blk` of tower t at (seed, step): rows x cols elements with

@@ -97,7 +97,8 @@ class Head(C.Structure):
 
 
 SCORES_MAX_CLASSES, SCORES_MAX_LABELS = 64, 128    # m2m_scores_multiclass / _multilabel limits (M2M_SCORES_MAX_*)
-FUSION_SUM, FUSION_MEAN, FUSION_MAX = 1, 2, 3      # m2m_fusion_forward / _backward modes (M2M_FUSION_*)
+RANK_STATE_WORDS = 4                               # uint32 words of a ranking buffer's state (M2M_RANK_STATE_WORDS)
+FUSION_SUM, FUSION_MEAN, FUSION_MAX = 1, 2, 3     # m2m_fusion_forward / _backward modes (M2M_FUSION_*)
 
 
 class Gate(C.Structure):
@@ -184,6 +185,9 @@ SIGNATURES = {
     # count tables of the scores (csrc/scores.hip): added into a uint64 device table
     "m2m_scores_multiclass": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
     "m2m_scores_multilabel": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp]),
+    # ranking buffers (csrc/rank.hip): softmax rows appended per step, four integers per row once per epoch
+    "m2m_rank_append": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_int64, _fp, _fp]),
+    "m2m_rank_counts": (C.c_int, [_fp, _fp, C.c_int, C.c_int64, C.c_int, C.c_int64, _fp, _fp]),
     "m2m_mlp_forward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, C.c_int, C.c_uint32, C.c_uint32,
                                   _fp, _fp]),
     "m2m_mlp_backward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, _fp]),

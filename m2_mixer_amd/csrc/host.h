@@ -15,6 +15,8 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 // ---- pack.hip, adam.hip, probes.hip: public entry points only (include/m2mixer.h); the packed slot they share: pack.h ----------
 
+// ---- scores.hip, rank.hip: public entry points only (include/m2mixer.h); they use m2m_set_error and ceil_div above -------------
+
 // ---- embed.hip -----------------------------------------------------------------------------------------------------------------
 int m2m_check_embed(const m2m_embed* e, int B);
 

@@ -147,7 +147,10 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
     An engine built with scores=True also counts the pass into its table of `split` (engine.score_table: cleared here at the
     start, read once at the end -- it stays readable until the next pass over the split) and the reference's scores derived
     from it are added under their own names (`f1m`, `prec_m`, `rec_m`, ..., `f1m_image`, ...: scores.TASK_SCORES); the keys
-    above keep their values -- the table's `acc` is the same quotient as the hit count's."""
+    above keep their values -- the table's `acc` is the same quotient as the hit count's.
+    An engine built with rank_scores=True also appends the pass to its ranking buffer of `split` (engine.rank_buffer: emptied
+    here at the start, counted once at the end) and the ranking scores are added under their own names (`ap_macro`,
+    `roc_auc_macro`, `ap_macro_image`, ...: scores.RANK_SCORES); the split must fit the engine's rank_capacity."""
     dev = engine.device
     table = None
     if getattr(engine, "scores", None) is not None:
@@ -155,6 +158,13 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
         table = engine.score_table("train" if train else (split if split != "train" else "train_eval"))
     if table is not None:
         table.reset()
+    rank = None
+    if getattr(engine, "rank", None) is not None:                  # rank_scores=True: the pass's ranking buffer, the same way
+        rank = engine.rank_buffer("train" if train else (split if split != "train" else "train_eval"))
+        rank.reset()
+    extra = {} if table is None else {"scores": table}
+    if rank is not None:
+        extra["rank"] = rank
     # [loss_a, loss_b, loss_fusion, loss] step sums | the same weighted by the step's batch size | hits a, b, fusion
     acc = torch.zeros(11, device=dev, dtype=torch.float64)
     seen, host = 0, np.zeros(11)
@@ -184,7 +194,7 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
             else:
                 eng.train_step(image, audio, labels, grad_sync=grad_sync)
         else:
-            eng.evaluate(image, audio, labels, **({} if table is None else {"scores": table}))
+            eng.evaluate(image, audio, labels, **extra)
         if eng is not engine and train:
             engine.pack()                                          # the tail step changed the weights
         acc[:4] += eng.losses                                      # device-side: no host round trip
@@ -198,6 +208,8 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
     steps, n = max(nb, 1), max(seen, 1)
     a, b = getattr(engine, "MODS", ("image", "audio"))
     out = {} if table is None else table.compute()
+    if rank is not None:
+        out.update(rank.compute())
     out.update({"loss": float(host[7]) / n, "loss_step_mean": float(host[3]) / steps,
             f"loss_{a}": float(host[0]) / steps, f"loss_{b}": float(host[1]) / steps, "loss_fusion": float(host[2]) / steps,
             "acc": float(host[10]) / n, f"acc_{a}": float(host[8]) / n, f"acc_{b}": float(host[9]) / n,

@@ -16,7 +16,9 @@ What changes relative to the module path (modules/mixer.py + torch autograd):
   * the step can be captured into a hipGraph (torch.cuda.CUDAGraph); the dropout step counter, the Adam
     step counter and the learning rate live in device memory so replays stay correct;
   * scores=True: the step also adds its batch's counts into an integer table on the device (ScoreTable, csrc/scores.hip), from
-    which accuracy / precision / recall / F1 under the reference's names are derived once per epoch (scores.py).
+    which accuracy / precision / recall / F1 under the reference's names are derived once per epoch (scores.py);
+  * rank_scores=True: the step also appends the softmax of its logits to a ranking buffer on the device (RankBuffer,
+    csrc/rank.hip), from which MIMIC's `auroc` (macro average precision) and ROC-AUC are derived once per epoch (scores.py).
 """
 from __future__ import annotations
 
@@ -204,6 +206,74 @@ class ScoreTable:
         return S.task_scores(self.task, self.counts().numpy(), self.head_names)
 
 
+class RankBuffer:
+    """The ranking buffer of one split in device memory: every step APPENDS the fp32 softmax of its batch's logits and the
+    labels (csrc/rank.hip: m2m_rank_append, one launch, capturable; the row cursor lives in `state` on the device), the host
+    asks once per epoch for four integers per row (m2m_rank_counts) and derives average precision / ROC-AUC in float64
+    (scores.rank_scores).  probs (nheads, K, capacity): a class column is contiguous; labels (capacity) int32, -1 where the
+    label was outside [0, K); state: L.RANK_STATE_WORDS uint32 (held as int32) = rows appended (keeps counting past capacity),
+    arrival ticket, rows without a label, reserved."""
+
+    def __init__(self, task: str, head_names: Sequence[str], K: int, capacity: int, device):
+        from . import scores as S
+        if task not in S.RANK_SCORES:
+            raise RuntimeError(f"RankBuffer: no ranking scores for task {task!r} (built: {', '.join(S.RANK_SCORES)}; multilabel "
+                               "ranking is not)")
+        self.task, self.head_names, self.K, self.capacity = task, tuple(head_names), int(K), int(capacity)
+        if not 1 <= self.K <= L.SCORES_MAX_CLASSES:
+            raise RuntimeError(f"RankBuffer: K = {K}: the ranking kernels take 1..{L.SCORES_MAX_CLASSES}")
+        if self.capacity < 1:
+            raise RuntimeError(f"RankBuffer: capacity = {capacity}: at least one row")
+        self.probs = torch.zeros(len(self.head_names), self.K, self.capacity, device=device)
+        self.labels = torch.full((self.capacity,), -1, dtype=torch.int32, device=device)
+        self.state = torch.zeros(L.RANK_STATE_WORDS, dtype=torch.int32, device=device)
+        self.skipped = None                          # rows without a label as of the last counts()
+
+    def add(self, logits: torch.Tensor, labels: torch.Tensor):
+        """Enqueue the launch that appends one batch: logits float32 (nheads, B, K), labels int64 (B).  Nothing synchronises."""
+        nh, B = len(self.head_names), int(logits.shape[1]) if logits.dim() == 3 else -1
+        want_x, want_l = (nh, B, self.K), (B,)
+        if (tuple(logits.shape) != want_x or tuple(labels.shape) != want_l or logits.dtype != torch.float32
+                or labels.dtype != torch.int64 or not logits.is_contiguous() or not labels.is_contiguous()
+                or logits.device != self.state.device or labels.device != self.state.device):
+            raise RuntimeError(f"RankBuffer.add: needs contiguous device tensors logits float32 ({nh}, B, {self.K}) and labels "
+                               f"int64 (B), got {tuple(logits.shape)} {logits.dtype} and {tuple(labels.shape)} {labels.dtype}")
+        L.check(L.lib().m2m_rank_append(logits.data_ptr(), labels.data_ptr(), nh, B, self.K, self.probs.data_ptr(),
+                                        self.labels.data_ptr(), self.capacity, self.state.data_ptr(), L.stream_ptr()), "rank_append")
+
+    def reset(self):
+        """Empty the buffer: an asynchronous fill of `state` on the current stream, in place -- captured graphs keep appending
+        into the same memory (the rows behind the cursor are dead)."""
+        self.state.zero_()
+
+    def rows(self) -> int:
+        """Rows appended since the last reset (one device-to-host copy; may exceed `capacity`: see counts)."""
+        return int(self.state[0].item()) & 0xFFFFFFFF
+
+    def counts(self) -> Tuple[torch.Tensor, torch.Tensor]:
+        """(counts (nheads, n, 4) int64 = n_ge, p_ge, n_gt, p_gt per row, labels (n) int64) on the host.  Reads `state`, launches
+        m2m_rank_counts over the n rows, copies back: the only synchronisation."""
+        st = self.state.cpu().numpy().view("uint32")
+        n = int(st[0])
+        if n > self.capacity:
+            raise RuntimeError(f"RankBuffer: overflow: capacity {self.capacity} rows, {n} rows seen since the last reset "
+                               "(rank_capacity= sets the capacity)")
+        self.skipped = int(st[2])
+        nh = len(self.head_names)
+        out = torch.zeros(nh, n, 4, dtype=torch.int32, device=self.state.device)
+        if n:
+            L.check(L.lib().m2m_rank_counts(self.probs.data_ptr(), self.labels.data_ptr(), nh, n, self.K, self.capacity,
+                                            out.data_ptr(), L.stream_ptr()), "rank_counts")
+        return out.cpu().to(torch.int64), self.labels[:n].cpu().to(torch.int64)
+
+    def compute(self, names: Optional[Sequence[str]] = None) -> Dict[str, float]:
+        """The task's ranking score names (scores.RANK_SCORES; `names`: any of auroc / ap_macro / roc_auc_macro) -> float
+        (fusion head: plain names; other heads: `_<modality>` appended)."""
+        from . import scores as S
+        counts, labels = self.counts()
+        return S.task_rank_scores(self.task, counts.numpy(), labels.numpy(), self.K, self.head_names, names)
+
+
 class _FlatEngine:
     """Flat parameter / gradient / Adam buffers, the optimizer, data-parallel hooks and hipGraph capture.
     Subclasses supply `_param_shapes(cfg)`, `_segment_of(key)`, `_build()` (which names `_towers` and `_embeds`),
@@ -215,7 +285,7 @@ class _FlatEngine:
     SCORES_TASK: str = ""
 
     def __init__(self, cfg: dict, batch_size: int, device, precision, lr, betas, eps, weight_decay, seed, init, share=None,
-                 scores: bool = False):
+                 scores: bool = False, rank_scores: bool = False, rank_capacity: int = 65536):
         """share: another engine of the same model; this one then works on ITS parameters, gradients, Adam state and
         step counters (its own activation buffers and packed operand copies, for another batch size) -- the second,
         smaller step that takes the ragged last batch of an epoch (data.run_epoch).  After a step on one of the two
@@ -281,6 +351,14 @@ class _FlatEngine:
             self.scores = share.scores
         elif scores:
             self.scores = self.new_score_table()
+        # rank_scores=True: every training step also appends the softmax of its logits and its labels to `self.rank` (RankBuffer;
+        # a sibling appends to its parent's), one launch where the count-table launch goes; off: no buffer, no launch
+        self.rank: Optional[RankBuffer] = None
+        self.rank_capacity = share.rank_capacity if share is not None else int(rank_capacity)
+        if share is not None:
+            self.rank = share.rank
+        elif rank_scores:
+            self.rank = self.new_rank_buffer()
         if init and share is None:
             self.reset_parameters(seed)
         self.logits = torch.zeros(3, self.B, self.K, device=dev)
@@ -589,12 +667,36 @@ class _FlatEngine:
         return not self._fused_heads
 
     def _score_forward(self, truth):
-        if self.scores is not None and self._preds_in_forward():
-            self.scores.add(self.preds, truth)
+        if self._preds_in_forward():
+            self._score_add(truth)
 
     def _score_backward(self, truth):
-        if self.scores is not None and not self._preds_in_forward():
+        if not self._preds_in_forward():
+            self._score_add(truth)
+
+    def _score_add(self, truth):
+        """Behind the launch that writes `preds` and `logits`: the count-table launch and / or the ranking append."""
+        if self.scores is not None:
             self.scores.add(self.preds, truth)
+        if self.rank is not None:
+            self.rank.add(self.logits, truth)
+
+    # ---- ranking buffers -------------------------------------------------------------------------------------
+    def new_rank_buffer(self) -> RankBuffer:
+        """An empty ranking buffer for this model's heads (one per split: evaluate(..., rank=buffer) appends to the one given)."""
+        return RankBuffer(self.SCORES_TASK, self.HEAD_NAMES, self.K, self.rank_capacity, self.device)
+
+    def rank_buffer(self, split: str) -> RankBuffer:
+        """The buffer of `split`, kept on the engine: "train" is the training buffer (`self.rank`, which needs
+        rank_scores=True), any other name gets a buffer of its own on first use."""
+        if split == "train":
+            if self.rank is None:
+                raise RuntimeError("rank_buffer('train'): this engine was built with rank_scores=False")
+            return self.rank
+        buffers = self.__dict__.setdefault("_split_ranks", {})
+        if split not in buffers:
+            buffers[split] = self.new_rank_buffer()
+        return buffers[split]
 
     def _check_trains(self):
         if self._eval_only:
@@ -730,6 +832,8 @@ class _FlatEngine:
         state = [self.flat_p, self.flat_m, self.flat_v, self.flat_g, self.adam_state, self.drop_step]
         if self.scores is not None:
             state.append(self.scores.table)          # (the warm-up steps count their batch too)
+        if self.rank is not None:
+            state.append(self.rank.state)            # (... and append it: the cursor goes back, the rows behind it are dead)
         snap = [t.clone() for t in state]
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream())
@@ -1117,12 +1221,15 @@ class _TwoTowerEngine(_FlatEngine):
         return [(lo, hi, mods[name]) for name, (lo, hi) in segs]
 
     @torch.no_grad()
-    def evaluate(self, xa, xb, labels, scores: Optional[ScoreTable] = None):
+    def evaluate(self, xa, xb, labels, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None):
         """validation/test step: dropout off (the reference's shared_step under model.eval()).  scores: a table
-        (new_score_table / score_table(split)) this batch's counts are added into."""
+        (new_score_table / score_table(split)) this batch's counts are added into.  rank: a ranking buffer (new_rank_buffer /
+        rank_buffer(split)) this batch's softmax rows are appended to."""
         self._forward(xa, xb, labels, False, False)
         if scores is not None:
             scores.add(self.preds, labels)
+        if rank is not None:
+            rank.add(self.logits, labels)
         a, b = self.MODS
         return {"logits": self.logits[2], f"{a}_logits": self.logits[0], f"{b}_logits": self.logits[1],
                 f"loss_{a}": self.losses[0], f"loss_{b}": self.losses[1], "loss_fusion": self.losses[2],
@@ -1137,13 +1244,15 @@ class AVMnistEngine(_TwoTowerEngine):
 
     def __init__(self, cfg: dict, batch_size: int, device="cuda:0", precision: Optional[str] = None,
                  lr: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 fusion_loss_weight: float = 1.0 / 3, seed: int = 42, init: bool = True, share=None, scores: bool = False):
+                 fusion_loss_weight: float = 1.0 / 3, seed: int = 42, init: bool = True, share=None, scores: bool = False,
+                 rank_scores: bool = False, rank_capacity: int = 65536):
         w = fusion_loss_weight
         ow = (1 - w) / 2
         # loss = (w Lf + ow Li + ow La) * 3      (models/avmnist.py:289-290)
         self.head_weights = {"image": 3 * ow, "audio": 3 * ow, "fusion": 3 * w}
         self.fusion_loss_weight = w
-        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share, scores)
+        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share, scores, rank_scores,
+                         rank_capacity)
 
     HEAD_NAMES = ("image", "audio", "fusion")
     SCORES_TASK = "avmnist"
@@ -1183,9 +1292,14 @@ class MMIMDBEngine(_TwoTowerEngine):
 
     def __init__(self, cfg: dict, batch_size: int, device="cuda:0", precision: Optional[str] = None,
                  lr: float = 1e-3, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 seed: int = 42, init: bool = True, share=None, scores: bool = False):
+                 seed: int = 42, init: bool = True, share=None, scores: bool = False,
+                 rank_scores: bool = False, rank_capacity: int = 65536):
         self.head_weights = {"image": 1.0, "text": 1.0, "fusion": 1.0}
-        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share, scores)
+        if rank_scores:
+            raise RuntimeError("MMIMDBEngine: rank_scores=True: multilabel ranking is not built (the ranking buffers take one "
+                               "label per sample: AVMnistEngine, MimicEngine)")
+        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share, scores, rank_scores,
+                         rank_capacity)
         self.pos_weight = torch.tensor(cfg["pos_weight"], dtype=torch.float32, device=self.device)
         if self.pos_weight.numel() != self.K:
             raise RuntimeError("pos_weight needs one entry per class")
@@ -1217,12 +1331,14 @@ class MimicEngine(_FlatEngine):
 
     def __init__(self, cfg: dict, batch_size: int, device="cuda:0", precision: Optional[str] = None,
                  lr: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
-                 fusion_loss_weight: float = 1.0 / 3, seed: int = 42, init: bool = True, share=None, scores: bool = False):
+                 fusion_loss_weight: float = 1.0 / 3, seed: int = 42, init: bool = True, share=None, scores: bool = False,
+                 rank_scores: bool = False, rank_capacity: int = 65536):
         w = fusion_loss_weight
         ow = (1 - w) / 2
         self.head_weights = {"static": ow, "time": ow, "fusion": w}
         self.fusion_loss_weight = w
-        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share, scores)
+        super().__init__(cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share, scores, rank_scores,
+                         rank_capacity)
 
     HEAD_NAMES = ("static", "time", "fusion")
     SCORES_TASK = "mimic"
@@ -1364,10 +1480,12 @@ class MimicEngine(_FlatEngine):
         main.wait_stream(s_f)
 
     @torch.no_grad()
-    def evaluate(self, static, time, labels, scores: Optional[ScoreTable] = None):
+    def evaluate(self, static, time, labels, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None):
         self._forward(static, time, labels, False, False)
         if scores is not None:
             scores.add(self.preds, labels)
+        if rank is not None:
+            rank.add(self.logits, labels)
         return {"logits": self.logits[2], "logits_static": self.logits[0], "logits_time": self.logits[1],
                 "loss_static": self.losses[0], "loss_time": self.losses[1], "loss_fusion": self.losses[2],
                 "loss": self.losses[3], "preds": self.preds[2]}

@@ -275,9 +275,12 @@ class _MultiLossModule(nn.Module):
         return dict(lr=oc.get("lr", oc.get("learning_rate", 1e-3)), betas=tuple(oc.get("betas", (0.9, 0.999))),
                     eps=oc.get("eps", 1e-8), weight_decay=oc.get("weight_decay", 0.0))
 
-    def to_engine(self, batch_size: int, precision: Optional[str] = None, scores: bool = False):
-        """The fused training engine (engine.py) over a copy of this module's weights.  scores: see bind_engine."""
-        eng = self._make_engine(self._engine_cfg(), batch_size, next(self.parameters()).device, precision, scores=scores)
+    def to_engine(self, batch_size: int, precision: Optional[str] = None, scores: bool = False, rank_scores: bool = False,
+                  rank_capacity: int = 65536):
+        """The fused training engine (engine.py) over a copy of this module's weights.  scores, rank_scores, rank_capacity: see
+        bind_engine."""
+        eng = self._make_engine(self._engine_cfg(), batch_size, next(self.parameters()).device, precision, scores=scores,
+                                rank_scores=rank_scores, rank_capacity=rank_capacity)
         eng.load_state_dict(self.state_dict())
         return eng
 
@@ -287,7 +290,8 @@ class _MultiLossModule(nn.Module):
         """The fused engine this module is bound to (bind_engine), or None."""
         return self._engine
 
-    def bind_engine(self, batch_size: int, precision: Optional[str] = None, scores: bool = False):
+    def bind_engine(self, batch_size: int, precision: Optional[str] = None, scores: bool = False, rank_scores: bool = False,
+                    rank_capacity: int = 65536):
         """Engine-backed mode: build the fused engine (engine.py) for `batch_size`, copy this module's weights into it, then
         point every parameter's `.data` at the engine's buffer (`engine.params[key]`): the Parameter objects stay the same,
         `parameters()`, `state_dict()`, `save_checkpoint()` read the live weights, and no copy is taken again.  From then on
@@ -299,7 +303,12 @@ class _MultiLossModule(nn.Module):
         scores=True: training_step / validation_step / test_step also add their batch's counts into the train / val / test count
         tables on the device (the reference's three setup_scores dictionaries; one small launch per step, inside the captured
         graph for training), and training_epoch_end / validation_epoch_end / test_epoch_end return the reference's scores.
-        Off (the default): no table, no launch."""
+        Off (the default): no table, no launch.
+        rank_scores=True (AV-MNIST, MIMIC): the steps also append the softmax of their logits to the train / val / test ranking
+        buffers on the device (engine.RankBuffer, `rank_capacity` rows each: a split must fit), and the three epoch-end hooks
+        return the ranking scores as well (scores.RANK_SCORES: MIMIC's `auroc`, the reference's name for macro average
+        precision, models/mimic.py:162-180; AV-MNIST `ap_macro`, `roc_auc_macro`) -- merged with the count-table scores, or on
+        their own with scores=False.  Off (the default): no buffer, no launch."""
         if self._engine is not None:
             raise RuntimeError("bind_engine: this module is already bound to an engine")
         if self.freeze_modalities_on_epoch is not None or self.modalities_freezed:
@@ -309,7 +318,8 @@ class _MultiLossModule(nn.Module):
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("bind_engine: the module must be on the GPU (.to('cuda')) first; the engine has no CPU path")
-        eng = self._make_engine(self._engine_cfg(), batch_size, dev, precision, scores=scores)
+        eng = self._make_engine(self._engine_cfg(), batch_size, dev, precision, scores=scores, rank_scores=rank_scores,
+                                rank_capacity=rank_capacity)
         eng.load_state_dict(self.state_dict())
         with torch.no_grad():
             for k, p in self.named_parameters():
@@ -437,12 +447,20 @@ class _MultiLossModule(nn.Module):
             return self.shared_step(batch, mode=mode)
         xa, xb, labels = self._engine_batch(batch, train=False)
         sib = self._eval_sibling(labels.shape[0])
-        table = self._score_table(mode)
-        if table is None:
-            sib.evaluate(xa.contiguous(), xb.contiguous(), labels.contiguous())
-        else:
-            sib.evaluate(xa.contiguous(), xb.contiguous(), labels.contiguous(), scores=table)
+        table, rank = self._score_table(mode), self._rank_buffer(mode)
+        extra = {} if table is None else {"scores": table}
+        if rank is not None:
+            extra["rank"] = rank
+        sib.evaluate(xa.contiguous(), xb.contiguous(), labels.contiguous(), **extra)
         return self._engine_eval_outputs(sib, batch, labels)
+
+    def _rank_buffer(self, split: str):
+        """The bound engine's ranking buffer of `split` ("train", "val", "test"); None when unbound or bound without
+        rank_scores."""
+        eng = self._engine
+        if eng is None or getattr(eng, "rank", None) is None:
+            return None
+        return eng.rank_buffer(split)
 
     def _score_table(self, split: str):
         """The bound engine's count table of `split` ("train", "val", "test"); None when unbound, bound without scores, or bound
@@ -455,11 +473,16 @@ class _MultiLossModule(nn.Module):
     def _epoch_scores(self, split: str) -> Optional[Dict[str, float]]:
         """compute() of `split`'s table under the reference's logging names (`<split>_<metric>`), then reset it -- what the
         torchmetrics objects do at an epoch end under Lightning.  One device-to-host copy."""
-        table = self._score_table(split)
-        if table is None:
+        table, rank = self._score_table(split), self._rank_buffer(split)
+        if table is None and rank is None:
             return None
-        out = {f"{split}_{k}": v for k, v in table.compute().items()}
-        table.reset()
+        out = {}
+        if table is not None:
+            out.update({f"{split}_{k}": v for k, v in table.compute().items()})
+            table.reset()
+        if rank is not None:                         # (bound with rank_scores=True: `<split>_auroc`, ... -- the buffer restarts empty)
+            out.update({f"{split}_{k}": v for k, v in rank.compute().items()})
+            rank.reset()
         return out
 
     def training_epoch_end(self, outputs=None) -> Optional[Dict[str, float]]:
@@ -545,10 +568,11 @@ class AVMnistMixerMultiLoss(_MultiLossModule):
     def _engine_batch(self, batch, train):
         return self._two_tower_batch(batch, train, batch["label"].long())
 
-    def _make_engine(self, cfg, batch_size, device, precision, scores=False):
+    def _make_engine(self, cfg, batch_size, device, precision, scores=False, rank_scores=False, rank_capacity=65536):
         from .engine import AVMnistEngine
         return AVMnistEngine(cfg, batch_size, device=device, precision=precision,
-                             fusion_loss_weight=self.fusion_loss_weight, init=False, scores=scores, **self._engine_kwargs())
+                             fusion_loss_weight=self.fusion_loss_weight, init=False, scores=scores, rank_scores=rank_scores,
+                            rank_capacity=rank_capacity, **self._engine_kwargs())
 
 
 class MMIMDBMixerMultiLoss(_MultiLossModule):
@@ -621,9 +645,10 @@ class MMIMDBMixerMultiLoss(_MultiLossModule):
         if any(not torch.equal(pw[0].cpu(), p.cpu()) for p in pw[1:]):
             raise RuntimeError("the bound engine takes one pos_weight for all three heads (models/mmimdb.py:47-50 builds them equal)")
 
-    def _make_engine(self, cfg, batch_size, device, precision, scores=False):
+    def _make_engine(self, cfg, batch_size, device, precision, scores=False, rank_scores=False, rank_capacity=65536):
         from .engine import MMIMDBEngine
-        return MMIMDBEngine(cfg, batch_size, device=device, precision=precision, init=False, scores=scores, **self._engine_kwargs())
+        return MMIMDBEngine(cfg, batch_size, device=device, precision=precision, init=False, scores=scores, rank_scores=rank_scores,
+                            rank_capacity=rank_capacity, **self._engine_kwargs())
 
 
 class MimicMixerMultiLoss(_MultiLossModule):
@@ -671,7 +696,8 @@ class MimicMixerMultiLoss(_MultiLossModule):
                 "loss_fusion": l[2], "loss_static": l[0], "loss_time": l[1], "logits": lg[2], "logits_static": lg[0],
                 "logits_time": lg[1]}
 
-    def _make_engine(self, cfg, batch_size, device, precision, scores=False):
+    def _make_engine(self, cfg, batch_size, device, precision, scores=False, rank_scores=False, rank_capacity=65536):
         from .engine import MimicEngine
         return MimicEngine(cfg, batch_size, device=device, precision=precision,
-                           fusion_loss_weight=self.fusion_loss_weight, init=False, scores=scores, **self._engine_kwargs())
+                           fusion_loss_weight=self.fusion_loss_weight, init=False, scores=scores, rank_scores=rank_scores,
+                            rank_capacity=rank_capacity, **self._engine_kwargs())

@@ -12,6 +12,9 @@ rule that differs between libraries.  This follows torchmetrics 0.11's `_adjust_
 package is not a dependency of this project and the rule is not pinned against it (tests pin it against scikit-learn where the
 two definitions coincide, and against a numpy restatement everywhere).
 
+Ranking scores (MIMIC's `auroc` = macro average precision, ROC-AUC) are functions of four integers per sample, produced on the
+device from a buffer of appended softmax rows (csrc/rank.hip, engine.RankBuffer): rank_scores / task_rank_scores below.
+
 No torch, no GPU: importable anywhere.
 """
 from __future__ import annotations
@@ -22,13 +25,18 @@ import numpy as np
 
 #: score names per task, for the fusion head, in the order of the reference's setup_scores dictionaries.  AV-MNIST: the four of
 #: AVMnistMixerMultiLoss (models/avmnist.py:366-380) then the three micro scores its single-loss variant adds (:56-78).
-#: MIMIC's `auroc` (a torchmetrics.AveragePrecision over ranked probabilities) is not a function of counts: not built.
+#: MIMIC's `auroc` (a torchmetrics.AveragePrecision over ranked probabilities) is no function of THESE tables: it comes from the
+#: ranking buffer's per-row counts (RANK_SCORES, rank_scores below).
 TASK_SCORES: Dict[str, Tuple[str, ...]] = {
     "avmnist": ("acc", "f1m", "prec_m", "rec_m", "f1mi", "prec_mi", "rec_mi"),
     "mimic": ("f1_micro", "acc", "precision_micro", "recall_micro"),
     "mmimdb": ("f1w", "f1m"),
 }
 TASK_KIND = {"avmnist": "multiclass", "mimic": "multiclass", "mmimdb": "multilabel"}
+#: ranking scores per task, for the fusion head (engine.RankBuffer, csrc/rank.hip).  MIMIC's `auroc` IS macro average precision:
+#: the reference builds torchmetrics.AveragePrecision under that name (models/mimic.py:162-180); the name is kept.  ROC-AUC is
+#: available on MIMIC too, as `roc_auc_macro` (task_rank_scores(..., names=...)).  Multilabel ranking (MM-IMDb) is not built.
+RANK_SCORES: Dict[str, Tuple[str, ...]] = {"mimic": ("auroc",), "avmnist": ("ap_macro", "roc_auc_macro")}
 
 
 def safe_divide(num, den):
@@ -113,4 +121,76 @@ def task_scores(task: str, counts, head_names: Sequence[str]) -> Dict[str, float
         suffix = "" if h == len(head_names) - 1 else "_" + head_names[h]
         for n in names:
             out[n + suffix] = s[_NAME_MAP[n]]
+    return out
+
+
+# ---- ranking scores: average precision and ROC-AUC from per-row counts -----------------------------------------------------------
+def rank_scores(counts, labels, K: int) -> Dict[str, object]:
+    """Per-class and macro average precision and ROC-AUC (one-vs-rest) of ONE head from its per-row counts.
+
+    counts (n, 4) integers {n_ge, p_ge, n_gt, p_gt} and labels (n) as m2m_rank_counts / engine.RankBuffer.counts() give them: for
+    row i of class c = labels[i] with score s_i = p_i[c], n_ge / p_ge = the rows / the class-c rows whose class-c score is >= s_i
+    (row i included), n_gt / p_gt the same with >; rows with label -1 carry zeros and were invisible to the others.  With
+    P_c = the rows of class c, N_c = the other labelled rows:
+
+      AP_c  = (1 / P_c) sum_{i: y_i = c} p_ge(i) / n_ge(i)
+      AUC_c = (1 / (P_c N_c)) sum_{i: y_i = c} [ N_c - (n_ge - p_ge) + ((n_ge - n_gt) - (p_ge - p_gt)) / 2 ]
+
+    Tied scores form one threshold, as in torchmetrics and scikit-learn: every positive of a tie group sees the whole group in
+    its >= counts (AP: the precision at the group's threshold), and a positive tied with a negative scores 1/2 (AUC).
+    Returns {"ap": (K,), "roc_auc": (K,), "ap_macro": float, "roc_auc_macro": float}; a class without positives is NaN in both
+    arrays, a class without negatives NaN in roc_auc.  Macro: the mean over the classes that are not NaN -- a class without
+    positives is left out of both means, one without negatives also out of roc_auc_macro; no class left: NaN.  Like
+    macro_class_weights this is torchmetrics' rule AS REMEMBERED and unpinned (scikit-learn agrees wherever every class has a
+    positive and a negative, which is what the tests pin).
+    A labelled row with n_ge == 0 did not count itself: its score is not finite (NaN compares false).  Everything is NaN then."""
+    c = np.asarray(counts).astype(np.int64).reshape(-1, 4)
+    y = np.asarray(labels).astype(np.int64).reshape(-1)
+    if c.shape[0] != y.shape[0]:
+        raise ValueError(f"{c.shape[0]} count rows for {y.shape[0]} labels")
+    if ((y < -1) | (y >= K)).any():
+        raise ValueError(f"labels must lie in [0, {K}) or be -1 (skipped)")
+    nan = float("nan")
+    ap, auc = np.full(K, nan), np.full(K, nan)
+    valid = y >= 0
+    if (c[valid, 0] == 0).any():
+        return {"ap": ap, "roc_auc": auc, "ap_macro": nan, "roc_auc_macro": nan}
+    nv = int(valid.sum())
+    n_ge, p_ge, n_gt, p_gt = (c[:, k].astype(np.float64) for k in range(4))
+    for k in range(int(K)):
+        rows = y == k
+        P = int(rows.sum())
+        N = nv - P
+        if P == 0:
+            continue
+        ap[k] = float((p_ge[rows] / n_ge[rows]).sum()) / P
+        if N > 0:
+            wins = N - (n_ge[rows] - p_ge[rows]) + 0.5 * ((n_ge[rows] - n_gt[rows]) - (p_ge[rows] - p_gt[rows]))
+            auc[k] = float(wins.sum()) / (float(P) * float(N))
+
+    def macro(v):
+        keep = ~np.isnan(v)
+        return float(v[keep].mean()) if keep.any() else nan
+
+    return {"ap": ap, "roc_auc": auc, "ap_macro": macro(ap), "roc_auc_macro": macro(auc)}
+
+
+# reference name -> key of rank_scores
+_RANK_NAME_MAP = {"auroc": "ap_macro", "ap_macro": "ap_macro", "roc_auc_macro": "roc_auc_macro"}
+
+
+def task_rank_scores(task: str, counts, labels, K: int, head_names: Sequence[str], names: Sequence[str] = None) -> Dict[str, float]:
+    """RANK_SCORES[task] (or `names`, any of auroc / ap_macro / roc_auc_macro) from the per-head row counts (nheads, n, 4) and the
+    n row labels: the LAST head is the fusion head and takes the plain names, the other heads `_<modality>`, as task_scores."""
+    names = RANK_SCORES[task] if names is None else tuple(names)
+    counts = np.asarray(counts)
+    if counts.ndim != 3 or counts.shape[0] != len(head_names) or counts.shape[2] != 4:
+        raise ValueError(f"counts must be ({len(head_names)}, n, 4), got {counts.shape}")
+    out: Dict[str, float] = {}
+    last = len(head_names) - 1
+    for h in [last] + list(range(last)):
+        s = rank_scores(counts[h], labels, K)
+        suffix = "" if h == last else "_" + head_names[h]
+        for n in names:
+            out[n + suffix] = s[_RANK_NAME_MAP[n]]
     return out
