@@ -9,7 +9,11 @@ step replayed as ONE graph takes ~2 ms (bench.py: `module_path_graphed`).  What 
 * torch.optim.Adam / AdamW with `capturable=True` (its step count lives on the device) and, to change the learning rate without
   re-capturing, `lr` as a device tensor: use `GraphedStep.set_lr`;
 * static input buffers: `__call__(batch)` copies the batch into them (same shapes as the example batch) and replays;
-* the warm-up steps capture needs are UNDONE (parameters, optimizer state): constructing a GraphedStep does not train.
+* the warm-up steps capture needs are UNDONE (parameters, optimizer state, the modules' dropout step counters): constructing a
+  GraphedStep does not train, and the first replay draws the dropout masks the next eager step would have drawn;
+* a replay runs no Python, so it advances no parameter's version counter (nor does an eager fused Adam): `__call__` marks the packed
+  operand copies of every tower / embedding module dirty after each replay (host attribute writes), so that a later `net.eval()`
+  forward -- which keeps packs whose version counters stand still -- re-packs from the weights the replay left.
 
 The module's `fusion_loss_weight` is a host float inside shared_step, so the graph keeps the value it was captured with: a loss-weight
 schedule (`fusion_loss_change`, validation_epoch_end) needs a new GraphedStep.  The engine-backed mode
@@ -41,7 +45,8 @@ class GraphedStep:
                 g["capturable"] = True
             # the fused implementation (one multi-tensor kernel instead of ~12 foreach passes over 33 MB): 2.06 -> 1.3 ms per
             # replayed step of M2-Mixer-B.  (It does not advance the parameters' version counters; the modules re-pack their
-            # operand copies unconditionally in training mode: modules/mixer.py, _train_repack.)
+            # operand copies unconditionally in training mode and leave them marked dirty for the next forward of another kind:
+            # modules/mixer.py, _train_repack / _pack.)
             if fused and all(p.is_cuda and torch.is_floating_point(p) for p in g["params"]):
                 g["fused"], g["foreach"] = True, False
             if not torch.is_tensor(g["lr"]):
@@ -63,6 +68,11 @@ class GraphedStep:
         snap_p = [p.detach().clone() for p in params]
         had_state = any(len(optimizer.state.get(p, {})) for p in params)
         snap_s = [{k: v.detach().clone() for k, v in optimizer.state.get(p, {}).items() if torch.is_tensor(v)} for p in params]
+        # ... and the dropout stream: every warm-up step and the captured one advance the modules' step counters (host mirror and,
+        # created by the first warm-up step, device counter)
+        droppers = [m for m in net.modules() if hasattr(m, "_drop_step")]
+        snap_d = [(m._drop_step, None if getattr(m, "_drop_counter", None) is None else m._drop_counter.clone()) for m in droppers]
+        self._packed = [m for m in net.modules() if hasattr(m, "invalidate_packs")]
         side = torch.cuda.Stream(device=dev)
         side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):
@@ -81,6 +91,13 @@ class GraphedStep:
                     if torch.is_tensor(v):
                         # a fresh optimizer's state is all zeros (moments, step count); a resumed one gets its values back
                         v.copy_(ss[k]) if (had_state and k in ss) else v.zero_()
+            for m, (step, ctr) in zip(droppers, snap_d):
+                m._drop_step = step
+                now = getattr(m, "_drop_counter", None)
+                if now is not None and ctr is not None and ctr.device == now.device:
+                    now.copy_(ctr)                      # in place: the graph holds the address
+                elif now is not None:
+                    now.fill_(step)                     # born in the warm-up, from the host value (_step_args)
         torch.cuda.synchronize(dev)
 
     def set_lr(self, lr: float) -> None:
@@ -93,4 +110,6 @@ class GraphedStep:
             if torch.is_tensor(v):
                 self.static[k].copy_(v, non_blocking=True)
         self.graph.replay()
+        for m in self._packed:
+            m.invalidate_packs()
         return self.out

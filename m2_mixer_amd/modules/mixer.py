@@ -29,6 +29,15 @@ def _train_repack(module: nn.Module) -> bool:
     return module.training and torch.is_grad_enabled()
 
 
+def _pack(rt, force: bool) -> None:
+    """Pack a tower or embedding runtime for this forward.  A forced pack belongs to a training step, whose optimizer may change
+    the weights behind the version counters AFTER this pack: the runtime is left marked dirty (a host flag, no launch), so the
+    next forward that does not force -- evaluation, a no_grad pass -- re-packs once.  (see _HipTower._runtime)"""
+    rt.pack(force=force)
+    if force:
+        rt.invalidate()
+
+
 def _param_holder_ff(dim: int, hidden: int, dropout: float, out_dim: Optional[int] = None) -> nn.Module:
     return FeedForward(dim, hidden, dropout, out_dim)
 
@@ -163,7 +172,8 @@ class _HipTower(nn.Module):
 
     def invalidate_packs(self):
         """The weights changed behind autograd's version counters (a fused engine trains them in place:
-        models._MultiLossModule.bind_engine): the next forward rebuilds the packed operand copies."""
+        models._MultiLossModule.bind_engine; a replayed GraphedStep; a `.data` edit): the next forward rebuilds the packed
+        operand copies.  Host attribute writes only."""
         for rt in self._rts or ():
             rt.invalidate()
         ert = getattr(self, "_ert", None)
@@ -179,7 +189,10 @@ class _HipTower(nn.Module):
     def _runtime(self) -> TowerRuntime:
         """The tower's TowerRuntime(s).  One m2m_tower holds at most L.MAX_BLOCKS MixerBlocks; a deeper tower (the reference's
         sweeps go to 16 mixers, sweeps/avmnist_mixer.yaml:19-35) is a chain of them -- `_rts`: consecutive chunks of blocks,
-        the final LayerNorm on the last chunk -- and forward / backward walk the chain.  `_rt` stays the first chunk."""
+        the final LayerNorm on the last chunk -- and forward / backward walk the chain.  `_rt` stays the first chunk.
+
+        Also brings the packed operand copies up to date, by the rule spelled out below: forced in a training step (which leaves
+        the runtimes dirty for the next forward of another kind), else when dirty or when a version counter moved."""
         all_blocks = [_block_tensors(b) for b in self._tower_blocks()]
         ln = self._final_ln()
         lnf = (ln.weight, ln.bias) if ln is not None else None
@@ -202,11 +215,16 @@ class _HipTower(nn.Module):
                     rt.bind_params(blocks, l)
         # Version counters catch in-place edits by ordinary ops (optimizers' foreach kernels, load_state_dict, p.mul_()) -- but NOT
         # torch's fused optimizers (torch.optim.Adam(fused=True) updates the values and leaves `_version` alone: measured on
-        # torch 2.10 / ROCm).  A module in training mode with gradients enabled is about to be stepped: re-pack unconditionally
-        # there (one ~12 us launch per tower, which a training step pays anyway); evaluation keeps the version check.
+        # torch 2.10 / ROCm), and not a replayed hipGraph, which runs no Python at all.  So the counters are only half of the rule:
+        #  * a module in training mode with gradients enabled is about to be stepped: it re-packs unconditionally (one ~12 us
+        #    launch per tower, which a training step pays anyway) and, since that pack precedes the step's optimizer update,
+        #    leaves its runtimes marked dirty (_pack);
+        #  * any other forward (evaluation, train mode under no_grad) re-packs when a runtime is dirty or a counter moved --
+        #    once: consecutive evaluations pack nothing;
+        #  * graphs.GraphedStep marks the runtimes dirty after every replay (invalidate_packs), as does whoever edits `.data`.
         force = _train_repack(self)
         for rt in self._rts:
-            rt.pack(force=force)
+            _pack(rt, force)
         self._rt = self._rts[0]
         return self._rt
 
@@ -294,7 +312,7 @@ class MLPMixer(_HipTower):
             self._ert.bind_params(conv.weight, conv.bias)
         elif self._ert.params_changed(conv.weight, conv.bias):
             self._ert.bind_params(conv.weight, conv.bias)
-        self._ert.pack(force=_train_repack(self))
+        _pack(self._ert, _train_repack(self))
         return _EmbedFunction.apply(x.contiguous().float(), self, conv.weight, conv.bias)
 
     def forward(self, x):
@@ -334,6 +352,6 @@ class MLPMixerNoPatching(_HipTower):
             self._ert.bind_params(self.proj.weight, self.proj.bias)
         elif self._ert.params_changed(self.proj.weight, self.proj.bias):
             self._ert.bind_params(self.proj.weight, self.proj.bias)
-        self._ert.pack(force=_train_repack(self))
+        _pack(self._ert, _train_repack(self))
         x0 = _EmbedFunction.apply(x.contiguous().float(), self, self.proj.weight, self.proj.bias)
         return self._run_tower(x0)

@@ -163,13 +163,17 @@ class TowerRuntime:
         self._packed_for = self._pack_versions()
 
     def invalidate(self):
-        """Call after editing a weight in a way autograd's version counter does not see (`p.data.copy_()`, `p.data = ...`):
-        the next pack() then rebuilds the packed copies."""
+        """Mark the packed copies dirty: the next pack() rebuilds them.  Call after (or, in a training step, ahead of) a change
+        of the weights that autograd's version counters do not see: `p.data.copy_()`, `p.data = ...`, torch's fused optimizers,
+        a replayed hipGraph."""
         self._packed_for = None
 
     def pack(self, force: bool = False):
-        """Refresh the packed MFMA-operand copies when the master weights changed (detected through the tensors' version
-        counters and, in bind_params, their storage; `.data` edits need invalidate())."""
+        """Refresh the packed MFMA-operand copies when `force` is set, when they are marked dirty (invalidate()), or when the
+        master weights changed as far as the tensors' version counters (and, in bind_params, their storage) show.  The counters
+        alone are not enough: torch.optim.Adam(fused=True) and hipGraph replays change the weights without advancing them, so
+        the module path forces the pack in training steps and invalidates after them (modules/mixer.py: _pack,
+        graphs.GraphedStep.__call__)."""
         if force or self._pack_versions() != self._packed_for:
             L.check(L.lib().m2m_pack_tower(C.byref(self.desc), L.stream_ptr()), "pack_tower")
             self.mark_packed()
