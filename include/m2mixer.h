@@ -349,6 +349,25 @@ int m2m_heads_ce_w(const m2m_head* heads, int nheads, const int64_t* labels, int
 int m2m_heads_bce_w(const m2m_head* heads, int nheads, const float* targets, const float* pos_weight, int B, int D, int K,
                     float* logits, float* losses, int32_t* preds, int zero_losses, const float* weights, void* stream);
 
+/* Evidential (EDL) heads (additive within ABI 18; csrc/edl.hip): models/avmnist.py:447-572 (AVMnistMixerMultiLossUQ) with
+ * modules/losses.py:5-31 (EDLMSELoss).  The heads of m2m_heads_ce_w -- same m2m_head fields, both input forms (pooled, or
+ * tokens / ntok / tok_sample_stride), same limits (D in {32, 64, 128, 256}, K in 2..32, 1..4 heads), same gradient contract
+ * (d_pooled written when non-NULL; g_w / g_b += with float atomics, or with g_part one [dW | db | 0 | 0] slot per workgroup,
+ * m2m_heads_part_tiles(B) slots per head, added by m2m_towers_wgrad_heads), same loss accumulation (zero_losses), same weights
+ * (NULL: m2m_head.weight; else nheads device floats) -- with the squared-error Bayes risk in place of the cross-entropy:
+ *   e = relu(z), a = e + 1, S = sum_k a_k, p = a / S;  L = sum_k [(y_k - p_k)^2 + p_k (1 - p_k) / (S + 1)]   (losses.py:24-31)
+ *   loss_h = mean over the batch; losses[nheads] = sum_h coef_h loss_h          (avmnist.py:511: coefficients 1, 1, 1)
+ * The reference's KL term is multiplied by annealing_coef * 0 (losses.py:20) and is left out: the epoch has no effect.
+ * Outputs: logits (nheads, B, K); losses (nheads + 1); preds (nheads, B) int32 = argmax_k relu(z), first index on ties, 0 when
+ * every logit is negative (avmnist.py:517-523); uncertainty (nheads, B) = K / S (:525-531); combined (B) int32 = preds_h of the
+ * head whose uncertainty is strictly below every other head's, 0 when there is none (:533-537).  The combination is a second
+ * small launch behind the heads launch on the same stream, one thread per sample, which reads its sample's per-head values
+ * before it writes: combined may alias preds + (nheads - 1) * B (that head's own predictions are then replaced).
+ * Everything is fp32.  Refusals (unsupported K / nheads / D / B, a NULL output): -1, m2m_last_error(), nothing launched. */
+int m2m_heads_edl(const m2m_head* heads, int nheads, const int64_t* labels, int B, int D, int K,
+                  float* logits, float* losses, int32_t* preds, float* uncertainty, int32_t* combined,
+                  int zero_losses, const float* weights, void* stream);
+
 /* m2m_towers_wgrad (above), which also adds the per-workgroup partial sums of the classification heads' weight gradients (m2m_head.g_part,
  * written by m2m_heads_ce at the same batch) to g_w / g_b: heads == NULL or nheads == 0: exactly m2m_towers_wgrad. */
 int m2m_towers_wgrad_heads(const m2m_tower* const* towers, const m2m_tower* const* dev_towers, int ntowers,

@@ -175,6 +175,8 @@ SIGNATURES = {
     # ABI 18: the heads' loss coefficients from device memory (the argument before the stream; NULL: m2m_head.weight)
     "m2m_heads_ce_w": (C.c_int, [C.POINTER(Head), C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, _fp, _fp]),
     "m2m_heads_bce_w": (C.c_int, [C.POINTER(Head), C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, _fp, _fp]),
+    # evidential heads (csrc/edl.hip): m2m_heads_ce_w's arguments + uncertainty and combined behind preds
+    "m2m_heads_edl": (C.c_int, [C.POINTER(Head), C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp]),
     # fusion functions other than ConcatFusion (csrc/fusion.hip)
     "m2m_fusion_forward": (C.c_int, [C.c_int, _fp, _fp, _fp, C.c_int64, _fp]),
     "m2m_fusion_backward": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_int64, _fp]),

@@ -2,6 +2,8 @@
 LightningModules as a fixed sequence of libm2mixer launches over flat fp32 parameter / gradient / Adam-state buffers.
 
   AVMnistEngine   AVMnistMixerMultiLoss   models/avmnist.py:236-312, :413-422   (two patch towers, CE, total x3)
+  AVMnistUQEngine AVMnistMixerMultiLossUQ models/avmnist.py:447-572            (AVMnistEngine with evidential losses, plain sum,
+                                                                                per-head uncertainty, combined prediction)
   MMIMDBEngine    MMIMDBMixerMultiLoss    models/mmimdb.py:96-147               (two patch towers, BCE(pos_weight), plain sum)
   MimicEngine     MimicMixerMultiLoss     models/mimic.py:93-142                (static MLP + time tower, CE, no x3)
 
@@ -32,7 +34,7 @@ import torch
 from . import _lib as L
 from . import config
 from .runtime import (AdamPackPlan, BLOCK_FIELDS, BLOCK_KEYS, EmbedRuntime, MlpRuntime, TowerRuntime, block_param_shapes, heads_bce,
-                      heads_ce, can_group, can_group_embeds, can_pack_all, embeds_forward, pack_all,
+                      heads_ce, heads_edl, can_group, can_group_embeds, can_pack_all, embeds_forward, pack_all,
                       towers_backward, towers_forward, towers_forward_embeds_ok, towers_wgrad, wgrad_slot_groups,
                       _embed_ptrs, _grad_ranges, _tower_ptrs)
 
@@ -969,7 +971,7 @@ class _TwoTowerEngine(_FlatEngine):
         # the heads' weight gradients: per-workgroup slots added in a fixed order by the weight-gradient launch instead of float
         # atomics -- with them a bf16 step is bit-reproducible (M2M_HEAD_SLOTS=0: atomics)
         self._head_part, self._wgrad_heads = None, None
-        if (self._heads_are_ce() and not self._fused_heads and config.switch_on("M2M_HEAD_SLOTS")
+        if (self._heads_write_slots() and not self._fused_heads and config.switch_on("M2M_HEAD_SLOTS")
                 and self.K * D + self.K + 2 <= L.SPLIT_GPART):
             self._head_part = torch.zeros(3, int(L.lib().m2m_heads_part_tiles(B)), L.SPLIT_GPART, device=dev)
         # the two modality towers' backward launch: slots instead of 128-way contended float atomics for the small gradients,
@@ -1079,6 +1081,11 @@ class _TwoTowerEngine(_FlatEngine):
     def _heads_are_ce(self) -> bool:
         """True: three cross-entropy heads (the form m2m_tower_backward_heads computes)."""
         return False
+
+    def _heads_write_slots(self) -> bool:
+        """True: the heads launch can leave its weight gradients in per-workgroup slots (m2m_head.g_part) for the weight-gradient
+        launch to add: the cross-entropy heads, and any engine whose own heads launch keeps that contract."""
+        return self._heads_are_ce()
 
     # ---- one training step (enqueue only; no host synchronisation) ----------------------------------------
     def _forward(self, xa, xb, labels, training: bool, with_grad: bool, prologue: bool = False):
@@ -1277,6 +1284,58 @@ class AVMnistEngine(_TwoTowerEngine):
     s_aud = property(lambda self: self.s_b)
     Ni = property(lambda self: self.Na)
     x0_img = property(lambda self: self.x0_a)
+
+
+class AVMnistUQEngine(AVMnistEngine):
+    """AVMnistEngine with the evidential heads of the reference's AVMnistMixerMultiLossUQ (models/avmnist.py:447-572): the three
+    cross-entropy losses become EDLMSELoss squared-error Bayes risks (modules/losses.py:5-31, m2m_heads_edl), every sample gets a
+    per-head uncertainty K / S, and the model's prediction is that of the least uncertain head.  Same parameters, same towers.
+
+      * loss = loss_image + loss_audio + loss_fusion (avmnist.py:511): coefficients 1, 1, 1, no fusion_loss_weight
+        (set_fusion_loss_weight is refused; set_loss_weights works, captured graphs follow it);
+      * `preds` (3, B) rows are [image, audio, combined] -- the reference's preds_image, preds_audio, preds: score tables,
+        data.run_epoch and evaluate() work unchanged and the plain score names mean the combined prediction (the fusion head's own
+        argmax is not kept; it is argmax relu(logits[2]));
+      * `uncertainty` (3, B) fp32 rows are [image, audio, fusion]; evaluate() returns them too.  A multi-step captured graph
+        (capture(steps > 1)) writes every step's values there: afterwards it holds the last step's;
+      * rank_scores=True is refused: the ranking buffers store a softmax, which is not this model's class probability."""
+
+    def __init__(self, cfg: dict, batch_size: int, device="cuda:0", precision: Optional[str] = None,
+                 lr: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
+                 seed: int = 42, init: bool = True, share=None, scores: bool = False,
+                 rank_scores: bool = False, rank_capacity: int = 65536):
+        if rank_scores:
+            raise RuntimeError("AVMnistUQEngine: rank_scores=True: the ranking buffers store the softmax of the logits, which is "
+                               "not the evidential model's class probability (alpha / S)")
+        self.head_weights = {"image": 1.0, "audio": 1.0, "fusion": 1.0}
+        # (past AVMnistEngine.__init__, which derives the coefficients from a fusion_loss_weight this model does not have)
+        _TwoTowerEngine.__init__(self, cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share, scores,
+                                 rank_scores, rank_capacity)
+        self.uncertainty = torch.zeros(3, self.B, device=self.device)
+
+    def set_fusion_loss_weight(self, w: float):
+        raise NotImplementedError("AVMnistUQEngine: its loss has no fusion_loss_weight (models/avmnist.py:511)")
+
+    def _loss_heads(self, heads, labels, zero_losses):
+        # (self.preds at call time: a multi-step capture points it at its per-step slots)
+        heads_edl(heads, labels, self.B, self.D, self.K,
+                  out=(self.logits, self.losses, self.preds, self.uncertainty, self.preds[2]), zero_losses=zero_losses,
+                  weights=self.loss_weights)
+
+    def _heads_are_ce(self) -> bool:
+        return False                                          # no fused heads + fusion-backward launch: that one computes cross-entropy
+
+    def _heads_write_slots(self) -> bool:
+        return True                                           # m2m_heads_edl keeps m2m_heads_ce's g_part contract
+
+    @torch.no_grad()
+    def evaluate(self, xa, xb, labels, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None):
+        """AVMnistEngine.evaluate; `preds` is the combined prediction, and the three uncertainties (B) are returned as well."""
+        if rank is not None:
+            raise RuntimeError("AVMnistUQEngine: ranking buffers are not built for the evidential model")
+        out = super().evaluate(xa, xb, labels, scores=scores)
+        out.update(uncertainty=self.uncertainty[2], uncertainty_image=self.uncertainty[0], uncertainty_audio=self.uncertainty[1])
+        return out
 
 
 class MMIMDBEngine(_TwoTowerEngine):

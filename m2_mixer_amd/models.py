@@ -1,6 +1,7 @@
 """The callers of the hot path: the reference's multi-loss task modules, Lightning-free.
 
     AVMnistMixerMultiLoss   models/avmnist.py:165-312, :413-422
+    AVMnistMixerMultiLossUQ models/avmnist.py:447-572 (evidential losses, per-head uncertainty, late fusion of the predictions)
     MimicMixerMultiLoss     models/mimic.py:24-142
     MMIMDBMixerMultiLoss    models/mmimdb.py:22-147
 
@@ -505,6 +506,8 @@ class _MultiLossModule(nn.Module):
 
     #: whether validation_epoch_end applies the fusion-loss-weight schedule (the reference's AV-MNIST and MIMIC models do)
     LOSS_SCHEDULE = True
+    #: whether the schedule reaches a bound engine (False: the model's loss ignores fusion_loss_weight, only the attribute moves)
+    ENGINE_LOSS_SCHEDULE = True
 
     def validation_epoch_end(self, outputs=None) -> Optional[Dict[str, float]]:
         """The loss-weight schedule of models/avmnist.py:338-339 / models/mimic.py:149-150: from epoch `loss_change_epoch` on,
@@ -518,7 +521,7 @@ class _MultiLossModule(nn.Module):
         new = min(1, self.fusion_loss_weight + self.fusion_loss_change)
         if new == self.fusion_loss_weight:
             return scores
-        if self._engine is not None:
+        if self._engine is not None and self.ENGINE_LOSS_SCHEDULE:
             self._engine.set_fusion_loss_weight(float(new))
         self.fusion_loss_weight = new
         return scores
@@ -573,6 +576,97 @@ class AVMnistMixerMultiLoss(_MultiLossModule):
         return AVMnistEngine(cfg, batch_size, device=device, precision=precision,
                              fusion_loss_weight=self.fusion_loss_weight, init=False, scores=scores, rank_scores=rank_scores,
                             rank_capacity=rank_capacity, **self._engine_kwargs())
+
+
+def edl_mse_loss(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """The reference's EDLMSELoss (modules/losses.py:5-31): the squared-error Bayes risk of the Dirichlet with evidence relu(logits),
+    batch mean.  Its KL term is multiplied by annealing_coef * 0 (losses.py:20) -- no value, no gradient, no effect of the epoch --
+    and is left out."""
+    alpha = torch.relu(logits) + 1.0
+    strength = alpha.sum(dim=-1, keepdim=True)
+    p = alpha / strength
+    target = torch.nn.functional.one_hot(labels, logits.shape[-1]).to(logits.dtype)
+    return ((target - p) ** 2 + p * (1 - p) / (strength + 1)).sum(dim=-1).mean()
+
+
+class EDLMSELoss(nn.Module):
+    """The reference's criterion module (modules/losses.py:5-31) around edl_mse_loss: no parameters, no buffers; `epoch_num` is
+    accepted and has no effect (the KL term it would anneal is times 0)."""
+
+    def __init__(self, num_classes: int, annealing_step: int = 10):
+        super().__init__()
+        self.num_classes, self.annealing_step = num_classes, annealing_step
+
+    def forward(self, output, y, epoch_num: int = 0):
+        return edl_mse_loss(output, y)
+
+
+class AVMnistMixerMultiLossUQ(AVMnistMixerMultiLoss):
+    """models/avmnist.py:447-572: AVMnistMixerMultiLoss with three EDLMSELoss criteria (which hold no parameters or buffers: the
+    state-dict keys are the parent's), loss = loss_image + loss_audio + loss_fusion (:511; fusion_loss_weight is ignored),
+    per-head uncertainties K / S and `preds` = the prediction of the strictly least uncertain head (:533-537).  Bound, it runs
+    engine.AVMnistUQEngine; the inherited fusion_loss_change schedule still moves the module attribute, as in the reference, and
+    does not reach the engine."""
+
+    ENGINE_LOSS_SCHEDULE = False
+
+    def __init__(self, model_cfg, optimizer_cfg, **kwargs):
+        super().__init__(model_cfg, optimizer_cfg, **kwargs)
+        self.num_classes = self.model_cfg.modalities.classification.num_classes
+        self.image_criterion = EDLMSELoss(self.num_classes, 10)                                   # models/avmnist.py:451-453
+        self.audio_criterion = EDLMSELoss(self.num_classes, 10)
+        self.fusion_criterion = EDLMSELoss(self.num_classes, 10)
+
+    def shared_step(self, batch, **kwargs):
+        image, audio, labels = batch["image"], batch["audio"], batch["label"]
+        mode = kwargs.get("mode", None)
+        mute = self._maybe_freeze_and_mute(mode)
+        if mode == "train" and mute == "image":
+            image = torch.zeros_like(image)
+        elif mode == "train" and mute == "audio":
+            audio = torch.zeros_like(audio)
+        image_tok = self.image_mixer(image)                                                       # models/avmnist.py:485-500
+        audio_tok = self.audio_mixer(audio)
+        fused = self.fusion_mixer(self.fusion_function(image_tok, audio_tok))
+        image_logits = self.classifier_image(image_tok.mean(dim=1))
+        audio_logits = self.classifier_audio(audio_tok.mean(dim=1))
+        logits = self.classifier_fusion(fused)
+        loss_image = self.image_criterion(image_logits, labels, self.current_epoch)               # :503-505
+        loss_audio = self.audio_criterion(audio_logits, labels, self.current_epoch)
+        loss_fusion = self.fusion_criterion(logits, labels, self.current_epoch)
+        loss = loss_image + loss_audio + loss_fusion                                              # :511
+        if self.modalities_freezed and mode == "train":
+            loss = loss_fusion
+        ev, ev_i, ev_a = torch.relu(logits), torch.relu(image_logits), torch.relu(audio_logits)  # :517-531
+        preds, preds_image, preds_audio = ev.argmax(dim=1), ev_i.argmax(dim=1), ev_a.argmax(dim=1)
+        u, u_i, u_a = (self.num_classes / (e + 1).sum(dim=1) for e in (ev, ev_i, ev_a))
+        combined = (preds * ((u < u_i) & (u < u_a)).long() + preds_image * ((u_i < u) & (u_i < u_a)).long()
+                    + preds_audio * ((u_a < u) & (u_a < u_i)).long())                             # :533-537
+        return {"preds": combined, "preds_image": preds_image, "preds_audio": preds_audio, "labels": labels, "loss": loss,
+                "loss_image": loss_image, "loss_audio": loss_audio, "loss_fusion": loss_fusion, "image_logits": image_logits,
+                "audio_logits": audio_logits, "logits": logits, "uncertainty": u.mean(), "uncertainty_image": u_i.mean(),
+                "uncertainty_audio": u_a.mean()}
+
+    @staticmethod
+    def _engine_uncertainties(eng) -> Dict[str, torch.Tensor]:
+        """shared_step's three batch means from the engine's (3, B) buffer (rows image, audio, fusion): new tensors."""
+        m = eng.uncertainty.mean(dim=1)
+        return {"uncertainty": m[2], "uncertainty_image": m[0], "uncertainty_audio": m[1]}
+
+    def _engine_train_outputs(self, eng, labels):
+        out = super()._engine_train_outputs(eng, labels)          # `preds`: the engine's row 2, the combined prediction
+        out.update(self._engine_uncertainties(eng))
+        return out
+
+    def _engine_eval_outputs(self, eng, batch, labels):
+        out = super()._engine_eval_outputs(eng, batch, labels)
+        out.update(self._engine_uncertainties(eng))
+        return out
+
+    def _make_engine(self, cfg, batch_size, device, precision, scores=False, rank_scores=False, rank_capacity=65536):
+        from .engine import AVMnistUQEngine
+        return AVMnistUQEngine(cfg, batch_size, device=device, precision=precision, init=False, scores=scores,
+                               rank_scores=rank_scores, rank_capacity=rank_capacity, **self._engine_kwargs())
 
 
 class MMIMDBMixerMultiLoss(_MultiLossModule):

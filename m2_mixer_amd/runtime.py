@@ -807,3 +807,28 @@ def heads_ce(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: int
         L.check(L.lib().m2m_heads_ce(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(),
                                      preds.data_ptr(), int(zero_losses), L.stream_ptr()), "heads_ce")
     return logits, losses, preds
+
+
+def heads_edl(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: int, out=None, zero_losses: bool = True,
+              weights: Optional[torch.Tensor] = None):
+    """Evidential heads (m2m_heads_edl: models/avmnist.py:447-572 with modules/losses.py:5-31): heads as for heads_ce.
+    Returns logits (nh, B, K), losses (nh + 1), preds (nh, B) int32 = argmax relu(logits), uncertainty (nh, B) = K / S and
+    combined (B) int32, the prediction of the strictly least uncertain head (0 when there is none) -- written into `out` if given,
+    where `combined` may be the last row of `preds` (that head's own predictions are then replaced).
+    weights: the heads' loss coefficients as a device tensor, None: each head's `weight`."""
+    nh = len(heads)
+    _check_weights(weights, nh)
+    arr = _head_array(heads)
+    dev = labels.device
+    if out is not None:
+        logits, losses, preds, uncertainty, combined = out
+    else:
+        logits = torch.empty(nh, B, K, device=dev)
+        losses = torch.empty(nh + 1, device=dev)
+        preds = torch.empty(nh, B, dtype=torch.int32, device=dev)
+        uncertainty = torch.empty(nh, B, device=dev)
+        combined = torch.empty(B, dtype=torch.int32, device=dev)
+    L.check(L.lib().m2m_heads_edl(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(), preds.data_ptr(),
+                                  uncertainty.data_ptr(), combined.data_ptr(), int(zero_losses), L.ptr(weights), L.stream_ptr()),
+            "heads_edl")
+    return logits, losses, preds, uncertainty, combined
