@@ -575,6 +575,43 @@ int m2m_rank_append(const float* logits, const int64_t* labels, int nheads, int 
 int m2m_rank_counts(const float* probs, const int32_t* row_labels, int nheads, int64_t n, int K, int64_t capacity, uint32_t* counts,
                     void* stream);
 
+/* ---- epoch feed: a captured step fetches its own batch (additive within ABI 18; csrc/feed.hip) ------------------------------------
+ * The reference shuffles its MIMIC and MM-IMDb training loaders (datasets/mimic.py:85, datasets/mmimdb.py:65).  With the split's
+ * tensors, a permutation and a cursor in device memory, one launch at the head of a captured step fills the step's static input
+ * slots, and one at its tail adds the step's losses and hit counts into the epoch's accumulators: a replayed graph takes no
+ * argument from the host and an epoch is read back once.
+ *
+ * state: M2M_FEED_STATE_WORDS uint32 the caller writes at an epoch start:
+ *   [0] cursor: rows handed out so far (keeps counting past n; 32 bits)
+ *   [1] reserved for an arrival ticket; zero (the gather as built takes none: see below)
+ *   [2] n: rows of the split, 1 <= n < 2^31 (0: the gather copies nothing)
+ *   [3] wrapped rows: every gather adds max(0, cursor + B - n) -- non-zero tells the host that a step ran past the epoch's end
+ *
+ *   m2m_feed_gather       for every batch row r < B and every source: row perm[(cursor + r) % n] of `src` (rows of row_bytes bytes,
+ *                         back to back) is copied to row r of `dst`; perm NULL: row (cursor + r) % n.  perm holds n values in
+ *                         [0, n): the modulo then keeps every read inside the split.  cursor and n are read from `state` on the
+ *                         device (a replayed graph has no host cursor); a one-thread launch enqueued behind the gather by the
+ *                         same call advances the cursor by B -- stream order keeps it behind every read of the cursor.
+ *                         16 bytes per lane where row_bytes, src and dst are multiples of 16, else 4.  row_bytes: a positive
+ *                         multiple of 4; src and dst 4-byte aligned; B * row_bytes / 4 < 2^31; 1 <= nsrc <= M2M_FEED_MAX_SOURCES.
+ *                         `srcs` is host memory, read before the call returns.
+ *   m2m_epoch_accumulate  sums[0..nloss) += losses, sums[nloss..2 nloss) += losses * B (float64); counts[h] += the rows with
+ *                         preds[h][row] == labels[row] (preds (nheads, B) int32, labels (B) int64) for h < nheads;
+ *                         counts[nheads] += 1 (steps), counts[nheads + 1] += B (samples).  nheads = 0: preds and labels may be
+ *                         NULL (multilabel predictions have no hit count).  One workgroup, no atomics: launches on one stream
+ *                         are ordered.  nloss >= 1, B >= 1.
+ * Both return -1 (m2m_last_error) and launch nothing on a NULL pointer or a size outside these bounds. */
+#define M2M_FEED_MAX_SOURCES 4
+#define M2M_FEED_STATE_WORDS 4
+typedef struct m2m_feed_src {
+    const void* src;
+    void* dst;
+    int64_t row_bytes;
+} m2m_feed_src;
+int m2m_feed_gather(const m2m_feed_src* srcs, int nsrc, const int32_t* perm, int B, uint32_t* state, void* stream);
+int m2m_epoch_accumulate(const float* losses, int nloss, const int32_t* preds, const int64_t* labels, int nheads, int B, double* sums,
+                         uint64_t* counts, void* stream);
+
 /* ---- test hooks ----------------------------------------------------------------------------------- */
 /* keep-mask (uint8, 1 keep) the kernels use for dropout site `site` (0 tok hidden, 1 tok out,
  * 2 channel hidden, 3 channel out) of block `blk` of tower t at (seed, step): rows x cols elements with

@@ -99,6 +99,12 @@ class Head(C.Structure):
 SCORES_MAX_CLASSES, SCORES_MAX_LABELS = 64, 128    # m2m_scores_multiclass / _multilabel limits (M2M_SCORES_MAX_*)
 RANK_STATE_WORDS = 4                               # uint32 words of a ranking buffer's state (M2M_RANK_STATE_WORDS)
 FUSION_SUM, FUSION_MEAN, FUSION_MAX = 1, 2, 3     # m2m_fusion_forward / _backward modes (M2M_FUSION_*)
+FEED_MAX_SOURCES, FEED_STATE_WORDS = 4, 4          # m2m_feed_gather (M2M_FEED_MAX_SOURCES, M2M_FEED_STATE_WORDS)
+
+
+class FeedSrc(C.Structure):
+    """m2m_feed_src"""
+    _fields_ = [("src", _fp), ("dst", _fp), ("row_bytes", C.c_int64)]
 
 
 class Gate(C.Structure):
@@ -190,6 +196,9 @@ SIGNATURES = {
     # ranking buffers (csrc/rank.hip): softmax rows appended per step, four integers per row once per epoch
     "m2m_rank_append": (C.c_int, [_fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_int64, _fp, _fp]),
     "m2m_rank_counts": (C.c_int, [_fp, _fp, C.c_int, C.c_int64, C.c_int, C.c_int64, _fp, _fp]),
+    # epoch feed (csrc/feed.hip): a captured step gathers its own batch and accumulates its own losses / hits
+    "m2m_feed_gather": (C.c_int, [C.POINTER(FeedSrc), C.c_int, _fp, C.c_int, _fp, _fp]),
+    "m2m_epoch_accumulate": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
     "m2m_mlp_forward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, C.c_int, C.c_uint32, C.c_uint32,
                                   _fp, _fp]),
     "m2m_mlp_backward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, _fp]),

@@ -89,6 +89,30 @@ class ResidentAVMnist:
                 yield image.index_select(0, idx), audio.index_select(0, idx), labels.index_select(0, idx)
 
 
+class ResidentTensors:
+    """Any task's splits resident in device memory: split name -> the tensors of the engine's batch, in its order (AV-MNIST:
+    image, audio, labels; MIMIC: static, time, labels; MM-IMDb: image, text, targets), all with the same number of rows.
+    ResidentAVMnist has the same `splits` / `device` and serves wherever one of these is taken.  (Loaders for MIMIC's im.pk and
+    MM-IMDb's files are out of scope: build the tensors, hand them in.)"""
+
+    def __init__(self, splits: Dict[str, Tuple[torch.Tensor, ...]], device=None):
+        self.splits: Dict[str, Tuple[torch.Tensor, ...]] = {}
+        self.device = torch.device(device) if device is not None else next(iter(splits.values()))[0].device
+        self.rank, self.world = 0, 1
+        for name, tensors in splits.items():
+            tensors = tuple(t.to(self.device).contiguous() for t in tensors)
+            if not tensors or any(t.dim() < 1 or t.shape[0] != tensors[0].shape[0] for t in tensors):
+                raise ValueError(f"{name}: every tensor of a split needs the same number of rows")
+            self.splits[name] = tensors
+
+    def num_samples(self, split: str) -> int:
+        return int(self.splits[split][0].shape[0])
+
+    def num_batches(self, split: str, batch_size: int, drop_last: bool = False) -> int:
+        n = self.num_samples(split)
+        return n // batch_size if drop_last else (n + batch_size - 1) // batch_size
+
+
 class PlateauLR:
     """torch.optim.lr_scheduler.ReduceLROnPlateau(mode='min', factor=0.1, threshold=1e-4 rel) on the engine's device-side
     learning rate (models/avmnist.py:416-422: monitor `val_loss`, patience from `scheduler_patience`)."""
@@ -215,4 +239,98 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
             "acc": float(host[10]) / n, f"acc_{a}": float(host[8]) / n, f"acc_{b}": float(host[9]) / n,
             "hits": int(round(host[10])), f"hits_{a}": int(round(host[8])), f"hits_{b}": int(round(host[9])),
             "steps": nb, "samples": seen})
+    return out
+
+
+def feed_plan(n: int, batch_size: int, steps: int, drop_last: bool = False) -> Tuple[int, int, int]:
+    """How a fed epoch over n samples runs: (replays of the `steps`-step graph, full batches left for single steps, rows of the
+    ragged tail -- 0 under drop_last).  Pure host arithmetic."""
+    if n < 0 or batch_size < 1 or steps < 1:
+        raise ValueError("feed_plan: n >= 0, batch_size >= 1, steps >= 1")
+    full = n // batch_size
+    return full // steps, full % steps, 0 if drop_last else n % batch_size
+
+
+def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = True, tail_engine=None, drop_last: bool = False,
+                  order=None, split: str = "train") -> Dict[str, float]:
+    """run_epoch with the batches fetched on the device (engine.EpochFeed): one pass over the first `n`
+    samples (default: all) of `order` (an index tensor for feed.start; None: the split's own order), every sample exactly once,
+    in order.  Any of the engines; single GPU.
+
+    train=True: `replay` is engine.capture_feed(feed, steps).  feed_plan(n, B, steps) replays of the graph, then the full
+    batches that do not fill a graph one at a time, eagerly (feed.gather_into + train_step + feed.accumulate on the graph's
+    first slots), then the ragged tail through `tail_engine` (default: the engine's kept training sibling of that size, which
+    must exist before the capture -- prepare_tail_engine's rule -- or engine.sibling(tail)), fed by gather_into, with pack()
+    before and after, as run_epoch does.  Nothing is read back until the end.
+    train=False: `replay` is unused (None); every batch is gathered eagerly, evaluated and accumulated.
+
+    Returns run_epoch's keys from feed.read(): loss, loss_step_mean, the per-head losses, steps, samples and -- for engines whose
+    predictions are classes -- acc*, hits*; the score table's and ranking buffer's numbers (scores=True / rank_scores=True) are
+    merged in as run_epoch does, under the table of `split`.  Ends with feed.check(): a pass that ran beyond the order raises."""
+    n = feed.n if n is None else int(n)
+    B = feed.B
+    if not 0 <= n <= feed.n:
+        raise ValueError(f"run_epoch_fed: n = {n} samples of a split of {feed.n}")
+    if B != engine.B:
+        raise ValueError(f"run_epoch_fed: the feed's batch size {B} is not the engine's {engine.B}")
+    which = "train" if train else (split if split != "train" else "train_eval")
+    table = engine.score_table(which) if getattr(engine, "scores", None) is not None else None
+    rank = engine.rank_buffer(which) if getattr(engine, "rank", None) is not None else None
+    for t in (table, rank):
+        if t is not None:
+            t.reset()
+    extra = {} if table is None else {"scores": table}
+    if rank is not None:
+        extra["rank"] = rank
+    feed.bind(engine)
+    feed.start(order)
+    steps = replay.steps if train else 1
+    replays, singles, tail = feed_plan(n, B, steps, drop_last)
+    if train:
+        if replay.feed is not feed:
+            raise ValueError("run_epoch_fed: `replay` was captured on another feed")
+        for _ in range(replays):
+            replay()
+        slots = replay.slots[0]
+        for _ in range(singles):
+            feed.gather_into(slots)
+            engine.train_step(*slots)
+            feed.accumulate(engine, slots[-1])
+    else:
+        slots = feed.new_slots()
+        for _ in range(replays * steps + singles):
+            feed.gather_into(slots)
+            engine.evaluate(*slots, **extra)
+            feed.accumulate(engine, slots[-1])
+    if tail:
+        if tail_engine is None:
+            tail_engine = engine._tail_engines.get(tail) if train else None
+        if tail_engine is None:
+            tail_engine = engine.sibling(tail, trains=train)
+            if train:
+                engine._tail_engines[tail] = tail_engine
+        tslots = feed.new_slots(tail)
+        tail_engine.pack()                                         # its packed copies missed every step since its last use
+        feed.gather_into(tslots)
+        if train:
+            tail_engine.train_step(*tslots)
+            engine.pack()                                          # the tail step changed the weights
+        else:
+            tail_engine.evaluate(*tslots, **extra)
+        feed.accumulate(tail_engine, tslots[-1])
+    sums, counts = feed.read()                                     # the only sync of the epoch
+    feed.check()
+    nl, nh = feed.nloss, feed.nheads
+    nsteps, seen = int(counts[nh]), int(counts[nh + 1])
+    a, b = engine.HEAD_NAMES[:2]                                    # (image, audio) / (image, text) / (static, time)
+    out = {} if table is None else table.compute()
+    if rank is not None:
+        out.update(rank.compute())
+    ds, dn = max(nsteps, 1), max(seen, 1)
+    out.update({"loss": float(sums[nl + 3]) / dn, "loss_step_mean": float(sums[3]) / ds,
+                f"loss_{a}": float(sums[0]) / ds, f"loss_{b}": float(sums[1]) / ds, "loss_fusion": float(sums[2]) / ds,
+                "steps": nsteps, "samples": seen})
+    if nh == 3:
+        out.update({"acc": int(counts[2]) / dn, f"acc_{a}": int(counts[0]) / dn, f"acc_{b}": int(counts[1]) / dn,
+                    "hits": int(counts[2]), f"hits_{a}": int(counts[0]), f"hits_{b}": int(counts[1])})
     return out

@@ -276,6 +276,132 @@ class RankBuffer:
         return S.task_rank_scores(self.task, counts.numpy(), labels.numpy(), self.K, self.head_names, names)
 
 
+class EpochFeed:
+    """One split's resident tensors behind a device-side permutation and cursor (csrc/feed.hip): a step
+    gathers its own batch (m2m_feed_gather: rows perm[(cursor + r) % n] of every source into the step's input slots, the cursor
+    advanced on the device) and adds its own losses and hit counts to the epoch's accumulators (m2m_epoch_accumulate) -- both
+    capturable, so a graph from engine.capture_feed replays without arguments and an epoch is read back once.
+
+    sources: the split's tensors in the engine's batch order (AV-MNIST: image, audio, labels), contiguous, on `device`, with the
+    dtypes the engine's inputs have; rows of a multiple of 4 bytes.  The feed owns
+      perm    (n) int32, the epoch's sample order
+      state   L.FEED_STATE_WORDS uint32 (held as int32): cursor, reserved (zero), n, wrapped rows
+      sums    (2 * nloss) float64: step losses | the same weighted by the step's batch size
+      counts  (nheads + 2) int64: hits per head | steps | samples
+    nloss / nheads follow the first engine the feed is used with (multilabel predictions have no hit count: nheads = 0).
+    Single GPU only: every rank of a data-parallel run would need its shard of the order (out of scope)."""
+
+    def __init__(self, sources: Sequence[torch.Tensor], batch_size: int, device):
+        self.device = torch.device(device)
+        self.sources = tuple(sources)
+        self.B = int(batch_size)
+        if not 1 <= len(self.sources) <= L.FEED_MAX_SOURCES:
+            raise ValueError(f"EpochFeed: 1..{L.FEED_MAX_SOURCES} sources, got {len(self.sources)}")
+        if self.B < 1:
+            raise ValueError("EpochFeed: batch_size >= 1")
+        self.n = int(self.sources[0].shape[0])
+        if not 1 <= self.n < 2 ** 31:
+            raise ValueError(f"EpochFeed: the split needs 1 <= n < 2^31 rows, got {self.n}")
+        for i, t in enumerate(self.sources):
+            if t.device != self.device or not t.is_contiguous() or t.dim() < 1 or int(t.shape[0]) != self.n:
+                raise ValueError(f"EpochFeed: source {i} must be a contiguous tensor of {self.n} rows on {self.device}")
+            if self._row_bytes(t) < 4 or self._row_bytes(t) % 4:
+                raise ValueError(f"EpochFeed: source {i} has rows of {self._row_bytes(t)} bytes; the gather copies multiples of 4")
+        self.perm = torch.arange(self.n, dtype=torch.int32, device=self.device)
+        self._state0 = torch.tensor([0, 0, self.n, 0], dtype=torch.int32, device=self.device)
+        self.state = self._state0.clone()
+        self._acc: Optional[torch.Tensor] = None         # sums and counts in one 8-byte-cell buffer: one copy reads both
+        self.nloss = self.nheads = None
+        self.sums = self.counts = None
+
+    @staticmethod
+    def _row_bytes(t: torch.Tensor) -> int:
+        return int(t[0].numel()) * t.element_size()
+
+    def bind(self, engine):
+        """Size the accumulators for `engine`'s losses and heads (first use), or check that they fit it."""
+        nloss = int(engine.losses.numel())
+        nheads = int(engine.preds.shape[0]) if engine.preds.dim() == 2 else 0
+        if self._acc is None:
+            self.nloss, self.nheads = nloss, nheads
+            self._acc = torch.zeros(2 * nloss + nheads + 2, dtype=torch.int64, device=self.device)
+            self.sums, self.counts = self._acc[:2 * nloss].view(torch.float64), self._acc[2 * nloss:]
+        elif (nloss, nheads) != (self.nloss, self.nheads):
+            raise RuntimeError(f"EpochFeed: accumulators sized for {self.nloss} losses / {self.nheads} heads, the engine has "
+                               f"{nloss} / {nheads}")
+
+    def new_slots(self, batch_size: Optional[int] = None) -> Tuple[torch.Tensor, ...]:
+        """Zeroed input slots of one step: the sources' row shapes and dtypes at `batch_size` rows (default: the feed's)."""
+        B = self.B if batch_size is None else int(batch_size)
+        return tuple(torch.zeros(B, *t.shape[1:], dtype=t.dtype, device=self.device) for t in self.sources)
+
+    def start(self, order=None):
+        """Begin an epoch: write its sample order (a host or device index tensor of n values in [0, n); None: identity) IN PLACE
+        and zero the cursor, the wrapped count and the accumulators, all on the current stream -- captured graphs keep reading
+        the same memory.  A given order is checked against [0, n) first (the one synchronisation: an index outside the split
+        would read outside it)."""
+        if order is None:
+            torch.arange(self.n, out=self.perm)
+        else:
+            order = torch.as_tensor(order)
+            if order.dim() != 1 or int(order.numel()) != self.n or order.dtype.is_floating_point or order.dtype == torch.bool:
+                raise ValueError(f"EpochFeed.start: the order must hold {self.n} integer indices, got {tuple(order.shape)} {order.dtype}")
+            lo, hi = (int(v) for v in torch.stack((order.min(), order.max())).cpu())
+            if lo < 0 or hi >= self.n:
+                raise ValueError(f"EpochFeed.start: the order's indices span [{lo}, {hi}], the split has rows [0, {self.n})")
+            self.perm.copy_(order.to(torch.int32))
+        self.state.copy_(self._state0)
+        if self._acc is not None:
+            self._acc.zero_()
+
+    def _state_host(self):
+        return self.state.cpu().numpy().view("uint32")
+
+    def rows(self) -> int:
+        """Rows handed out since start() (the cursor; one device-to-host copy)."""
+        return int(self._state_host()[0])
+
+    def check(self):
+        """Raise when a gather ran past the end of the epoch (its rows wrapped around to the order's head)."""
+        st = self._state_host()
+        if int(st[3]):
+            raise RuntimeError(f"EpochFeed: {int(st[0])} rows were fed from a split of {self.n}: {int(st[3])} row(s) wrapped around "
+                               "to the head of the order (a replay past the end of the epoch)")
+
+    def read(self):
+        """(sums float64 (2 * nloss), counts int64 (nheads + 2)) on the host as numpy: one copy, the epoch's only synchronisation."""
+        if self._acc is None:
+            raise RuntimeError("EpochFeed.read: no engine has used this feed yet")
+        host = self._acc.cpu().numpy()
+        return host[:2 * self.nloss].view("float64").copy(), host[2 * self.nloss:].copy()
+
+    def gather_into(self, slots: Sequence[torch.Tensor]):
+        """Enqueue the gather of the next slots[0].shape[0] rows of the order into `slots` (one per source, as new_slots makes
+        them; any batch size: the ragged tail's engine has its own).  Nothing synchronises."""
+        if len(slots) != len(self.sources):
+            raise ValueError(f"EpochFeed.gather_into: {len(self.sources)} slots (one per source), got {len(slots)}")
+        B = int(slots[0].shape[0])
+        desc = (L.FeedSrc * len(slots))()
+        for d, s, t in zip(desc, self.sources, slots):
+            if (t.dtype != s.dtype or tuple(t.shape) != (B, *s.shape[1:]) or not t.is_contiguous() or t.device != self.device):
+                raise ValueError(f"EpochFeed.gather_into: a slot must be a contiguous {s.dtype} tensor ({B}, {', '.join(map(str, s.shape[1:]))}) "
+                                 f"on {self.device}, got {t.dtype} {tuple(t.shape)}")
+            d.src, d.dst, d.row_bytes = s.data_ptr(), t.data_ptr(), self._row_bytes(s)
+        L.check(L.lib().m2m_feed_gather(desc, len(slots), self.perm.data_ptr(), B, self.state.data_ptr(), L.stream_ptr()), "feed_gather")
+
+    def accumulate(self, engine, labels: Optional[torch.Tensor]):
+        """Enqueue the launch that adds `engine`'s step (its losses, its preds against `labels`, its batch size) to the epoch's
+        accumulators.  Nothing synchronises."""
+        self.bind(engine)
+        preds = engine.preds if self.nheads else None
+        if self.nheads and (labels is None or labels.dtype != torch.int64 or tuple(labels.shape) != (engine.B,) or not labels.is_contiguous()
+                            or preds.dtype != torch.int32 or not preds.is_contiguous()):
+            raise RuntimeError(f"EpochFeed.accumulate: hit counts need contiguous labels int64 ({engine.B},) and preds int32")
+        L.check(L.lib().m2m_epoch_accumulate(engine.losses.data_ptr(), self.nloss, L.ptr(preds), L.ptr(labels) if self.nheads else 0,
+                                             self.nheads, engine.B, self.sums.data_ptr(), self.counts.data_ptr(), L.stream_ptr()),
+                "epoch_accumulate")
+
+
 class _FlatEngine:
     """Flat parameter / gradient / Adam buffers, the optimizer, data-parallel hooks and hipGraph capture.
     Subclasses supply `_param_shapes(cfg)`, `_segment_of(key)`, `_build()` (which names `_towers` and `_embeds`),
@@ -894,6 +1020,77 @@ class _FlatEngine:
             return out_losses                     # this graph's own buffer: (4,) or, for a multi-step graph, (steps, 4)
 
         replay.losses = out_losses
+        return replay
+
+    def capture_feed(self, feed: EpochFeed, steps: int = 1, grad_sync=None):
+        """Capture `steps` consecutive training steps that feed themselves from `feed` (EpochFeed); returns a callable replay()
+        without arguments.  Each captured step is: m2m_feed_gather into that step's input slots (the cursor advances on the
+        device), fused_step on the slots, m2m_epoch_accumulate of its losses and hits into the feed's accumulators -- so an epoch
+        is n / (B * steps) replays and one feed.read().  feed.start(order) between replays changes the order in place; the graph
+        follows it.  replay.slots[i] are step i's input slots, replay.losses the (4,) / (steps, 4) loss buffer as for capture().
+        Like capture() it does not train: the warm-up steps are undone, the feed's cursor and accumulators included.
+        Single GPU only: a grad_sync is refused (every rank would need its shard of the order)."""
+        if grad_sync is not None:
+            raise ValueError("capture_feed is only supported without a gradient exchange (single GPU)")
+        if steps < 1:
+            raise ValueError("capture_feed: steps >= 1")
+        if feed.B != self.B or feed.device != self.device:
+            raise ValueError(f"capture_feed: the feed's batch size / device ({feed.B}, {feed.device}) are not the engine's "
+                             f"({self.B}, {self.device})")
+        self._check_trains()
+        feed.bind(self)
+        slots = [feed.new_slots() for _ in range(steps)]
+
+        def fed_step(i):
+            feed.gather_into(slots[i])
+            self.fused_step(*slots[i])
+            feed.accumulate(self, slots[i][-1])
+
+        # as capture(): the warm-up runs REAL steps; everything they change is put back -- here the feed's state too
+        state = [self.flat_p, self.flat_m, self.flat_v, self.flat_g, self.adam_state, self.drop_step, feed.state, feed._acc]
+        if self.scores is not None:
+            state.append(self.scores.table)
+        if self.rank is not None:
+            state.append(self.rank.state)
+        snap = [t.clone() for t in state]
+        s = torch.cuda.Stream(device=self.device)
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                fed_step(0)
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        for dst, src in zip(state, snap):
+            dst.copy_(src)
+        self.pack()
+        torch.cuda.synchronize()
+
+        out_losses = self.losses
+        home = (self.losses, self.logits, self.preds)
+        if steps > 1:                                   # per-step output slots of THIS graph, as capture(steps > 1)
+            losses_steps = torch.zeros(steps, *self.losses.shape, device=self.device)
+            logits_steps = torch.zeros(steps, *self.logits.shape, device=self.device)
+            preds_steps = torch.zeros(steps, *self.preds.shape, dtype=self.preds.dtype, device=self.device)
+            out_losses = losses_steps
+        g = torch.cuda.CUDAGraph()
+        try:
+            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+                for i in range(steps):
+                    if steps > 1:
+                        self.losses, self.logits, self.preds = losses_steps[i], logits_steps[i], preds_steps[i]
+                    fed_step(i)
+        finally:
+            self.losses, self.logits, self.preds = home
+        self._slots_folded = False
+        self._graph = (g,)
+
+        def replay():
+            g.replay()
+            return out_losses
+
+        replay.losses, replay.slots, replay.steps, replay.feed = out_losses, slots, steps, feed
+        if steps > 1:
+            replay.logits, replay.preds = logits_steps, preds_steps
         return replay
 
 
