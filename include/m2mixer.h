@@ -600,15 +600,29 @@ int m2m_rank_counts(const float* probs, const int32_t* row_labels, int nheads, i
  *                         counts[nheads] += 1 (steps), counts[nheads + 1] += B (samples).  nheads = 0: preds and labels may be
  *                         NULL (multilabel predictions have no hit count).  One workgroup, no atomics: launches on one stream
  *                         are ordered.  nloss >= 1, B >= 1.
- * Both return -1 (m2m_last_error) and launch nothing on a NULL pointer or a size outside these bounds. */
+ *   m2m_feed_gather_muted m2m_feed_gather with a muting schedule read on the device (stage two of the reference's two-stage
+ *                         training zeroes one input per training step: models/avmnist.py:243-256).  codes: ncodes int32 in device
+ *                         memory, one per step of the epoch: 0 mutes nothing ("multimodal"), s + 1 mutes source s.  The step index
+ *                         is mute_state[0] (M2M_FEED_MUTE_STATE_WORDS uint32 in device memory, zeroed by the caller at an epoch
+ *                         start).  The muted source's rows are not read: its `dst` rows are filled with zero bytes (what
+ *                         torch.zeros_like gives); every other source is copied exactly as m2m_feed_gather copies it.  The
+ *                         decision is uniform per 1024-unit tile: no atomics, no LDS.  The one-thread launch behind the gather
+ *                         also does mute_state[0] += 1; a step index >= ncodes mutes nothing and does mute_state[1] += 1 (the
+ *                         host then knows that steps ran past the schedule).  A code outside [0, nsrc] mutes nothing.
+ *                         Refused (-1, nothing launched): NULL mute_state, NULL codes with ncodes > 0, ncodes < 0, and whatever
+ *                         m2m_feed_gather refuses.
+ * All return -1 (m2m_last_error) and launch nothing on a NULL pointer or a size outside these bounds. */
 #define M2M_FEED_MAX_SOURCES 4
 #define M2M_FEED_STATE_WORDS 4
+#define M2M_FEED_MUTE_STATE_WORDS 2
 typedef struct m2m_feed_src {
     const void* src;
     void* dst;
     int64_t row_bytes;
 } m2m_feed_src;
 int m2m_feed_gather(const m2m_feed_src* srcs, int nsrc, const int32_t* perm, int B, uint32_t* state, void* stream);
+int m2m_feed_gather_muted(const m2m_feed_src* srcs, int nsrc, const int32_t* perm, int B, uint32_t* state, const int32_t* codes, int ncodes,
+                          uint32_t* mute_state, void* stream);
 int m2m_epoch_accumulate(const float* losses, int nloss, const int32_t* preds, const int64_t* labels, int nheads, int B, double* sums,
                          uint64_t* counts, void* stream);
 

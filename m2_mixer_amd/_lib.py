@@ -100,6 +100,7 @@ SCORES_MAX_CLASSES, SCORES_MAX_LABELS = 64, 128    # m2m_scores_multiclass / _mu
 RANK_STATE_WORDS = 4                               # uint32 words of a ranking buffer's state (M2M_RANK_STATE_WORDS)
 FUSION_SUM, FUSION_MEAN, FUSION_MAX = 1, 2, 3     # m2m_fusion_forward / _backward modes (M2M_FUSION_*)
 FEED_MAX_SOURCES, FEED_STATE_WORDS = 4, 4          # m2m_feed_gather (M2M_FEED_MAX_SOURCES, M2M_FEED_STATE_WORDS)
+FEED_MUTE_STATE_WORDS = 2                          # m2m_feed_gather_muted: step index, steps past the schedule
 
 
 class FeedSrc(C.Structure):
@@ -198,6 +199,7 @@ SIGNATURES = {
     "m2m_rank_counts": (C.c_int, [_fp, _fp, C.c_int, C.c_int64, C.c_int, C.c_int64, _fp, _fp]),
     # epoch feed (csrc/feed.hip): a captured step gathers its own batch and accumulates its own losses / hits
     "m2m_feed_gather": (C.c_int, [C.POINTER(FeedSrc), C.c_int, _fp, C.c_int, _fp, _fp]),
+    "m2m_feed_gather_muted": (C.c_int, [C.POINTER(FeedSrc), C.c_int, _fp, C.c_int, _fp, _fp, C.c_int, _fp, _fp]),
     "m2m_epoch_accumulate": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
     "m2m_mlp_forward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, C.c_int, C.c_uint32, C.c_uint32,
                                   _fp, _fp]),

@@ -7,6 +7,10 @@
 // the host, and an epoch is read back once.
 //
 // The gather is a pure copy: no float arithmetic, no LDS, no atomics.
+//
+// m2m_feed_gather_muted is the same gather with a muting schedule in device memory: per step one source may
+// be zero-filled instead of copied (stage two of the reference's two-stage training); its advance launch also moves the schedule's
+// step index.  m2m_feed_gather's kernels and launches are not shared with it, only the host-side checks are.
 #include "host.h"
 
 #define FD_THREADS 256
@@ -85,6 +89,82 @@ __global__ __launch_bounds__(64) void feed_advance_kernel(int B, unsigned int* s
     state[1] = 0u;
 }
 
+// ---- the muted gather (m2m_feed_gather_muted): stage two of the reference's two-stage training zeroes one input per step -------
+// feed_copy_tile with the tile's muting decision taken BETWEEN its index phase and its data phase.  The step's code is the end of
+// a dependent pair of loads (mute_state[0] -> codes[step]) as the row index is (state -> perm[...]).  The kernel asks for the code
+// through the VECTOR memory path before the tile loop (code_v: every lane the same address) and this function makes it uniform
+// only after the perm loads are out: vector loads return in order, so waiting for the code leaves the perm loads in flight, and
+// the two pairs overlap.  (As a scalar load ahead of the branch the code sat on every workgroup's critical path -- scalar loads
+// are waited for all at once, and the source descriptors are scalar loads too: +0.9 us on a 26.8 us launch at M2-Mixer-B,
+// DESIGN.md section 14.)  A muted tile stores zero bytes (what torch.zeros_like gives) and reads no source row; its perm entries
+// were read.
+template <typename T>
+__device__ __forceinline__ void feed_tile_muted(const FeedSource& f, unsigned int u0, const int32_t* __restrict__ perm, unsigned int c0,
+                                                unsigned int n, int s, int code_v) {
+    unsigned int row[FD_UNROLL], col[FD_UNROLL], idx[FD_UNROLL];
+    T v[FD_UNROLL];
+    const unsigned int last = f.units - 1u;
+#pragma unroll
+    for (int j = 0; j < FD_UNROLL; ++j) {
+        const unsigned int u = min(u0 + j * FD_THREADS + threadIdx.x, last);
+        row[j] = u / f.units_per_row;
+        col[j] = u - row[j] * f.units_per_row;
+        const unsigned int at = (c0 + row[j]) % n;
+        idx[j] = perm ? (unsigned int)perm[at] : at;
+    }
+    const int muted = __builtin_amdgcn_readfirstlane(code_v) - 1;                 // -1: nothing (a code outside [1, nsrc] matches no source)
+    if (s == muted) {                                                             // workgroup-uniform
+        memset(v, 0, sizeof(v));
+    } else {
+#pragma unroll
+        for (int j = 0; j < FD_UNROLL; ++j)
+            v[j] = *reinterpret_cast<const T*>(f.src + (long long)idx[j] * f.row_bytes + (long long)col[j] * (long long)sizeof(T));
+    }
+#pragma unroll
+    for (int j = 0; j < FD_UNROLL; ++j)
+        if (u0 + j * FD_THREADS + threadIdx.x <= last)
+            *reinterpret_cast<T*>(f.dst + (long long)row[j] * f.row_bytes + (long long)col[j] * (long long)sizeof(T)) = v[j];
+}
+
+// feed_gather_kernel with a muting schedule: codes[mute_state[0]] is 0 (mute nothing) or s + 1 (mute source s); a step index past
+// the schedule mutes nothing.  The code is one uniform load per workgroup, the decision is per tile (a tile belongs to one source):
+// no atomics, no LDS, no ticket.  mute_state is only READ here; feed_advance_muted_kernel behind it moves the step index.
+__global__ __launch_bounds__(FD_THREADS) void feed_gather_muted_kernel(const FeedArgs a, const int32_t* __restrict__ perm,
+                                                                       const unsigned int* __restrict__ state,
+                                                                       const int32_t* __restrict__ codes, int ncodes,
+                                                                       const unsigned int* __restrict__ mute_state) {
+    const unsigned int cursor = state[0], n = state[2], mstep = mute_state[0];
+    // (all three uniform loads in flight together: without this the compiler sinks each below the branch before its first use and
+    // waits for them one after the other)
+    asm volatile("" ::"s"(cursor), "s"(n), "s"(mstep));
+    if (n == 0 || n >= 0x80000000u) return;
+    const unsigned int c0 = cursor % n;
+    int code_v = 0;                                                               // (lane offset 0, opaque to the compiler: a vector load)
+    if (mstep < (unsigned int)(ncodes > 0 ? ncodes : 0)) code_v = codes[mstep + __builtin_amdgcn_mbcnt_lo(0u, 0u)];
+    for (unsigned int t = blockIdx.x; t < a.tiles; t += gridDim.x) {
+        int s = 0;
+        while (s + 1 < a.nsrc && t >= a.s[s + 1].tile0) ++s;
+        const FeedSource& f = a.s[s];
+        const unsigned int u0 = (t - f.tile0) * FD_TILE;
+        if (f.vec) feed_tile_muted<uint4>(f, u0, perm, c0, n, s, code_v);
+        else feed_tile_muted<unsigned int>(f, u0, perm, c0, n, s, code_v);
+    }
+}
+
+// feed_advance_kernel + the muting schedule's step index: mute_state[0] += 1; a step that ran past the schedule (it muted nothing)
+// is counted in mute_state[1].
+__global__ __launch_bounds__(64) void feed_advance_muted_kernel(int B, unsigned int* state, int ncodes, unsigned int* mute_state) {
+    if (threadIdx.x != 0) return;
+    const unsigned int cursor = state[0], n = state[2];
+    const unsigned int end = cursor + (unsigned int)B;
+    if (end > n) state[3] += end - n;
+    state[0] = end;
+    state[1] = 0u;
+    const unsigned int mstep = mute_state[0];
+    if (mstep >= (unsigned int)(ncodes > 0 ? ncodes : 0)) mute_state[1] += 1u;
+    mute_state[0] = mstep + 1u;
+}
+
 // One wavefront, no atomics (launches on one stream are ordered).  sums: 2 * nloss doubles; counts: nheads + 2 uint64.
 __global__ __launch_bounds__(64) void epoch_accumulate_kernel(const float* __restrict__ losses, int nloss, const int32_t* __restrict__ preds,
                                                               const int64_t* __restrict__ labels, int nheads, int B, double* sums,
@@ -110,7 +190,8 @@ __global__ __launch_bounds__(64) void epoch_accumulate_kernel(const float* __res
     }
 }
 
-extern "C" int m2m_feed_gather(const m2m_feed_src* srcs, int nsrc, const int32_t* perm, int B, uint32_t* state, void* stream) {
+// The checks and the tile list both gathers share; -1 (m2m_last_error) before anything is launched.
+static int feed_build_args(const m2m_feed_src* srcs, int nsrc, int B, const uint32_t* state, FeedArgs& a) {
     if (!srcs || !state) {
         m2m_set_error("feed: srcs and state must be given (no NULL pointers)", __FILE__, __LINE__);
         return -1;
@@ -123,7 +204,6 @@ extern "C" int m2m_feed_gather(const m2m_feed_src* srcs, int nsrc, const int32_t
         m2m_set_error("feed: gather needs B >= 1", __FILE__, __LINE__);
         return -1;
     }
-    FeedArgs a;
     a.nsrc = nsrc;
     unsigned long long tiles = 0;
     for (int i = 0; i < M2M_FEED_MAX_SOURCES; ++i) {
@@ -165,11 +245,38 @@ extern "C" int m2m_feed_gather(const m2m_feed_src* srcs, int nsrc, const int32_t
         return -1;
     }
     a.tiles = (unsigned int)tiles;
+    return 0;
+}
+
+extern "C" int m2m_feed_gather(const m2m_feed_src* srcs, int nsrc, const int32_t* perm, int B, uint32_t* state, void* stream) {
+    FeedArgs a;
+    if (int rc = feed_build_args(srcs, nsrc, B, state, a)) return rc;
     const unsigned int grid = a.tiles < FD_MAX_WG ? a.tiles : FD_MAX_WG;
     hipLaunchKernelGGL(feed_gather_kernel, dim3(grid), dim3(FD_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a, perm,
                        static_cast<const unsigned int*>(state));
     M2M_CHECK_HIP(hipGetLastError());
     hipLaunchKernelGGL(feed_advance_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), B, state);
+    M2M_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int m2m_feed_gather_muted(const m2m_feed_src* srcs, int nsrc, const int32_t* perm, int B, uint32_t* state, const int32_t* codes,
+                                     int ncodes, uint32_t* mute_state, void* stream) {
+    if (!mute_state) {
+        m2m_set_error("feed: the muted gather needs mute_state (no NULL pointer)", __FILE__, __LINE__);
+        return -1;
+    }
+    if (ncodes < 0 || (ncodes > 0 && !codes)) {
+        m2m_set_error("feed: ncodes >= 0, and ncodes > 0 needs codes (no NULL pointer)", __FILE__, __LINE__);
+        return -1;
+    }
+    FeedArgs a;
+    if (int rc = feed_build_args(srcs, nsrc, B, state, a)) return rc;
+    const unsigned int grid = a.tiles < FD_MAX_WG ? a.tiles : FD_MAX_WG;
+    hipLaunchKernelGGL(feed_gather_muted_kernel, dim3(grid), dim3(FD_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a, perm,
+                       static_cast<const unsigned int*>(state), codes, ncodes, static_cast<const unsigned int*>(mute_state));
+    M2M_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(feed_advance_muted_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), B, state, ncodes, mute_state);
     M2M_CHECK_HIP(hipGetLastError());
     return 0;
 }

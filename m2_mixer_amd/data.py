@@ -252,7 +252,7 @@ def feed_plan(n: int, batch_size: int, steps: int, drop_last: bool = False) -> T
 
 
 def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = True, tail_engine=None, drop_last: bool = False,
-                  order=None, split: str = "train") -> Dict[str, float]:
+                  order=None, split: str = "train", muting=None) -> Dict[str, float]:
     """run_epoch with the batches fetched on the device (engine.EpochFeed): one pass over the first `n`
     samples (default: all) of `order` (an index tensor for feed.start; None: the split's own order), every sample exactly once,
     in order.  Any of the engines; single GPU.
@@ -263,6 +263,8 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
     must exist before the capture -- prepare_tail_engine's rule -- or engine.sibling(tail)), fed by gather_into, with pack()
     before and after, as run_epoch does.  Nothing is read back until the end.
     train=False: `replay` is unused (None); every batch is gathered eagerly, evaluated and accumulated.
+    muting (train=True, a feed built with muting=True): the epoch's muting codes, one per training step (models.muting_codes),
+    handed to feed.start; evaluation never mutes (its schedule is all zeros).
 
     Returns run_epoch's keys from feed.read(): loss, loss_step_mean, the per-head losses, steps, samples and -- for engines whose
     predictions are classes -- acc*, hits*; the score table's and ranking buffer's numbers (scores=True / rank_scores=True) are
@@ -283,7 +285,9 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
     if rank is not None:
         extra["rank"] = rank
     feed.bind(engine)
-    feed.start(order)
+    if muting is not None and not train:
+        raise ValueError("run_epoch_fed: evaluation never mutes (muting= goes with train=True)")
+    feed.start(order, muting=muting)
     steps = replay.steps if train else 1
     replays, singles, tail = feed_plan(n, B, steps, drop_last)
     if train:

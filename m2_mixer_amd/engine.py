@@ -20,7 +20,11 @@ What changes relative to the module path (modules/mixer.py + torch autograd):
   * scores=True: the step also adds its batch's counts into an integer table on the device (ScoreTable, csrc/scores.hip), from
     which accuracy / precision / recall / F1 under the reference's names are derived once per epoch (scores.py);
   * rank_scores=True: the step also appends the softmax of its logits to a ranking buffer on the device (RankBuffer,
-    csrc/rank.hip), from which MIMIC's `auroc` (macro average precision) and ROC-AUC are derived once per epoch (scores.py).
+    csrc/rank.hip), from which MIMIC's `auroc` (macro average precision) and ROC-AUC are derived once per epoch (scores.py);
+  * freeze_modalities(): stage two of the reference's two-stage training (models/avmnist.py:292-293, :314-324) -- the loss is
+    loss_fusion alone, the modality towers, their embeddings and heads are never written again, and the step skips their
+    backward, weight gradients, Adam and re-pack; EpochFeed(muting=True) zeroes one input per step from
+    a schedule on the device (csrc/feed.hip: m2m_feed_gather_muted).
 """
 from __future__ import annotations
 
@@ -28,6 +32,7 @@ from collections import OrderedDict
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import ctypes as C
+import weakref
 
 import torch
 
@@ -145,6 +150,34 @@ def mimic_param_shapes(cfg: dict) -> "OrderedDict[str, tuple]":
     _head_shapes(s, ("static", "time", "fusion"), (st["output_dim"], t["hidden_dim"], cfg["multimodal"]["hidden_dim"]),
                  cfg["num_classes"])
     return s
+
+
+def trainable_flat_ranges(shapes: "Dict[str, tuple]", frozen_prefixes: Sequence[str]) -> List[Tuple[int, int]]:
+    """Stage two of the reference's two-stage training (models/avmnist.py:314-324): the contiguous flat ranges [lo, hi) of the
+    parameters that keep training, given the ordered state-dict shapes and the key prefixes that freeze.  Neighbouring trainable
+    parameters are merged; the ranges are sorted and disjoint, and with the frozen keys' ranges they tile [0, n_params).  Pure:
+    no device, no library."""
+    frozen = tuple(frozen_prefixes)
+    out: List[Tuple[int, int]] = []
+    off = 0
+    for k, shp in shapes.items():
+        cnt = 1
+        for d in shp:
+            cnt *= int(d)
+        if not k.startswith(frozen):
+            if out and out[-1][1] == off:
+                out[-1] = (out[-1][0], off + cnt)
+            else:
+                out.append((off, off + cnt))
+        off += cnt
+    return out
+
+
+def frozen_key_prefixes(names: Sequence[str]) -> Tuple[str, ...]:
+    """Key prefixes that stage two freezes for the modalities `names` (_MultiLossModule._freeze_modalities): the two modality
+    towers with their embeddings (MIMIC: static_extractor, time_mixer) and their two heads."""
+    towers = ("static_extractor.", "time_mixer.") if tuple(names) == ("static", "time") else tuple(f"{n}_mixer." for n in names)
+    return towers + tuple(f"classifier_{n}." for n in names)
 
 
 def _exchange_mode(grad_sync) -> str:
@@ -289,9 +322,15 @@ class EpochFeed:
       sums    (2 * nloss) float64: step losses | the same weighted by the step's batch size
       counts  (nheads + 2) int64: hits per head | steps | samples
     nloss / nheads follow the first engine the feed is used with (multilabel predictions have no hit count: nheads = 0).
-    Single GPU only: every rank of a data-parallel run would need its shard of the order (out of scope)."""
+    Single GPU only: every rank of a data-parallel run would need its shard of the order (out of scope).
 
-    def __init__(self, sources: Sequence[torch.Tensor], batch_size: int, device):
+    muting=True (stage two's random modality muting, models/avmnist.py:243-256): the feed also owns
+      mute_codes  (ceil(n / B)) int32, one code per step of the epoch: 0 mutes nothing, s + 1 mutes source s (start writes them)
+      mute_state  L.FEED_MUTE_STATE_WORDS uint32 (held as int32): the step index, steps that ran past the schedule
+    and gather_into uses m2m_feed_gather_muted: the muted source's slot is filled with zero bytes, its rows are not read.
+    Both are allocated once: a captured graph keeps their pointers.  Off (the default): neither exists, nothing new is launched."""
+
+    def __init__(self, sources: Sequence[torch.Tensor], batch_size: int, device, muting: bool = False):
         self.device = torch.device(device)
         self.sources = tuple(sources)
         self.B = int(batch_size)
@@ -310,6 +349,10 @@ class EpochFeed:
         self.perm = torch.arange(self.n, dtype=torch.int32, device=self.device)
         self._state0 = torch.tensor([0, 0, self.n, 0], dtype=torch.int32, device=self.device)
         self.state = self._state0.clone()
+        self.mute_codes = self.mute_state = None
+        if muting:
+            self.mute_codes = torch.zeros((self.n + self.B - 1) // self.B, dtype=torch.int32, device=self.device)
+            self.mute_state = torch.zeros(L.FEED_MUTE_STATE_WORDS, dtype=torch.int32, device=self.device)
         self._acc: Optional[torch.Tensor] = None         # sums and counts in one 8-byte-cell buffer: one copy reads both
         self.nloss = self.nheads = None
         self.sums = self.counts = None
@@ -335,11 +378,26 @@ class EpochFeed:
         B = self.B if batch_size is None else int(batch_size)
         return tuple(torch.zeros(B, *t.shape[1:], dtype=t.dtype, device=self.device) for t in self.sources)
 
-    def start(self, order=None):
+    def start(self, order=None, muting=None):
         """Begin an epoch: write its sample order (a host or device index tensor of n values in [0, n); None: identity) IN PLACE
         and zero the cursor, the wrapped count and the accumulators, all on the current stream -- captured graphs keep reading
         the same memory.  A given order is checked against [0, n) first (the one synchronisation: an index outside the split
-        would read outside it)."""
+        would read outside it).
+        muting (a feed built with muting=True): the epoch's codes, one per step, at most ceil(n / B), each in [0, nsrc - 1] -- the
+        last source, the labels, cannot be muted; written in place, the rest of the schedule zero; None: all zeros.  The step
+        index and the overflow word are reset."""
+        codes = None
+        if muting is not None:
+            if self.mute_codes is None:
+                raise ValueError("EpochFeed.start: a muting schedule needs a feed built with muting=True")
+            codes = torch.as_tensor(muting).detach().cpu()
+            cap, hi_code = int(self.mute_codes.numel()), len(self.sources) - 1
+            if codes.dim() != 1 or codes.dtype.is_floating_point or codes.dtype == torch.bool or int(codes.numel()) > cap:
+                raise ValueError(f"EpochFeed.start: the muting schedule must hold at most {cap} integer codes, got "
+                                 f"{tuple(codes.shape)} {codes.dtype}")
+            if codes.numel() and (int(codes.min()) < 0 or int(codes.max()) > hi_code):
+                raise ValueError(f"EpochFeed.start: muting codes span [{int(codes.min())}, {int(codes.max())}]; allowed are 0 (nothing) "
+                                 f"and 1..{hi_code} (source s + 1; the last source, the labels, cannot be muted)")
         if order is None:
             torch.arange(self.n, out=self.perm)
         else:
@@ -351,6 +409,11 @@ class EpochFeed:
                 raise ValueError(f"EpochFeed.start: the order's indices span [{lo}, {hi}], the split has rows [0, {self.n})")
             self.perm.copy_(order.to(torch.int32))
         self.state.copy_(self._state0)
+        if self.mute_codes is not None:
+            self.mute_codes.zero_()
+            if codes is not None and codes.numel():
+                self.mute_codes[:codes.numel()].copy_(codes.to(torch.int32))
+            self.mute_state.zero_()
         if self._acc is not None:
             self._acc.zero_()
 
@@ -367,6 +430,11 @@ class EpochFeed:
         if int(st[3]):
             raise RuntimeError(f"EpochFeed: {int(st[0])} rows were fed from a split of {self.n}: {int(st[3])} row(s) wrapped around "
                                "to the head of the order (a replay past the end of the epoch)")
+        if self.mute_state is not None:
+            ms = self.mute_state.cpu().numpy().view("uint32")
+            if int(ms[1]):
+                raise RuntimeError(f"EpochFeed: {int(ms[0])} gathers ran against a muting schedule of {int(self.mute_codes.numel())} "
+                                   f"steps: {int(ms[1])} step(s) past its end muted nothing")
 
     def read(self):
         """(sums float64 (2 * nloss), counts int64 (nheads + 2)) on the host as numpy: one copy, the epoch's only synchronisation."""
@@ -387,6 +455,11 @@ class EpochFeed:
                 raise ValueError(f"EpochFeed.gather_into: a slot must be a contiguous {s.dtype} tensor ({B}, {', '.join(map(str, s.shape[1:]))}) "
                                  f"on {self.device}, got {t.dtype} {tuple(t.shape)}")
             d.src, d.dst, d.row_bytes = s.data_ptr(), t.data_ptr(), self._row_bytes(s)
+        if self.mute_codes is not None:
+            L.check(L.lib().m2m_feed_gather_muted(desc, len(slots), self.perm.data_ptr(), B, self.state.data_ptr(),
+                                                  self.mute_codes.data_ptr(), int(self.mute_codes.numel()), self.mute_state.data_ptr(),
+                                                  L.stream_ptr()), "feed_gather_muted")
+            return
         L.check(L.lib().m2m_feed_gather(desc, len(slots), self.perm.data_ptr(), B, self.state.data_ptr(), L.stream_ptr()), "feed_gather")
 
     def accumulate(self, engine, labels: Optional[torch.Tensor]):
@@ -464,6 +537,7 @@ class _FlatEngine:
         if share is not None:
             self.adam_state, self.drop_step = share.adam_state, share.drop_step
             self.loss_weights, self._loss_weight_group = share.loss_weights, share._loss_weight_group
+            self._stage_group = share._stage_group
         else:
             self.adam_state = torch.tensor([0.0, lr, 0.0, 0.0], device=dev)     # [step, lr, -, -]
             self.drop_step = torch.zeros(1, dtype=torch.int32, device=dev)       # device-side dropout step counter
@@ -471,6 +545,8 @@ class _FlatEngine:
             # graph follows set_fusion_loss_weight / set_loss_weights without being captured again
             self.loss_weights = torch.tensor(self._head_weight_list(), dtype=torch.float32, device=dev)
             self._loss_weight_group = {"fused_heads": False}      # (shared by the siblings, like the table itself)
+            # the training stage of the engine family (freeze_modalities): shared by existing and later siblings
+            self._stage_group = {"frozen": False, "weights": None, "members": []}
         self.seed = (share.seed if share is not None else seed) & 0xFFFFFFFF
         # scores=True: every training step ends its forward with one launch that adds the batch's counts into `self.scores`
         # (a sibling adds into its parent's table); off: no table, no launch -- the step is exactly the one without the feature
@@ -511,9 +587,15 @@ class _FlatEngine:
         self.s_fus = torch.cuda.Stream(device=dev)
         self.s_emb = torch.cuda.Stream(device=dev)
         self.concurrent = config.switch_on("M2M_CONCURRENT")      # 0: every launch on the main stream (A/B)
+        # the loss coefficients the heads launch of the current pass reads: loss_weights, or stage two's (0, 0, 1) in training
+        self._step_weights = self.loss_weights
+        self._trainable: List[Tuple[int, int]] = []      # stage two: the flat ranges Adam still updates (trainable_flat_ranges)
         self._build()
         if self._fused_heads:
             self._loss_weight_group["fused_heads"] = True
+        self._stage_group["members"].append(weakref.ref(self))
+        if self._frozen:
+            self._enter_stage_two()                  # a sibling built after freeze_modalities()
         self.pack()
 
     # ---- helpers for subclasses ----------------------------------------------------------------------------
@@ -719,6 +801,85 @@ class _FlatEngine:
             eng._ranges_add = [(lo, n, v, int(k and lo in other)) for lo, n, v, k in eng._ranges_add]
         return sib
 
+    # ---- stage two: frozen modality towers (models/avmnist.py:292-293, :314-324) -------------------------------------------
+    def _frozen_prefixes(self) -> Tuple[str, ...]:
+        return frozen_key_prefixes(self.HEAD_NAMES[:2])
+
+    @property
+    def _frozen(self) -> bool:
+        return self._stage_group["frozen"]
+
+    def freeze_modalities(self):
+        """Enter stage two of the reference's two-stage training, for this engine, its siblings and siblings built later (there
+        is no way back: the reference has none).  From the next training step on
+          * the training loss is loss_fusion with coefficient 1: training passes read a second device table (0, 0, 1), evaluation
+            keeps `loss_weights` and its schedule; losses[0..2] are still the three heads' losses, losses[3] == losses[2];
+          * the parameters and both Adam moments of the frozen keys (the two modality towers with their embeddings and heads) are
+            never written again; the shared step count keeps advancing, so the trainable ranges' bias correction continues;
+          * the step launches no backward of a frozen tower, no embedding gradient, the weight gradients of the fusion tower
+            alone, Adam over the trainable ranges only and the re-pack of the fusion tower only.
+        Captured graphs are dropped as release_capture() drops them: capture again.  Refused with M2M_FUSED_HEADS=1 (that launch
+        takes the loss weights by value); a gradient exchange is refused in stage two (single GPU)."""
+        grp = self._stage_group
+        if grp["frozen"]:
+            return
+        if self._loss_weight_group["fused_heads"]:
+            raise RuntimeError("freeze_modalities: the fused heads + fusion backward launch (M2M_FUSED_HEADS=1) takes the loss "
+                               "weights by value; stage two needs that switch off")
+        grp["weights"] = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float32, device=self.device)
+        grp["frozen"] = True
+        members = [m for m in (r() for r in grp["members"]) if m is not None]
+        grp["members"] = [weakref.ref(m) for m in members]
+        # Stage one left the ranges its overwriting weight-gradient launch owned uncleared ("keep").  A range stage two's
+        # single-tower call accumulates into instead (another row plan: no slot) must start from zero: clear every trainable range
+        # once, here, outside any graph.
+        for lo, hi in trainable_flat_ranges(self.shapes, self._frozen_prefixes()):
+            self.flat_g[lo:hi].zero_()
+        for m in members:
+            m._enter_stage_two()
+        # one gradient buffer: a range one engine leaves uncleared must be overwritten by every other training engine (sibling())
+        trains = [m for m in members if not m._eval_only]
+        for m in trains:
+            others = [{r[0] for r in o._ranges_add} for o in trains if o is not m]
+            m._ranges_add = [(lo, n, v, int(k and all(lo in o for o in others))) for lo, n, v, k in m._ranges_add]
+
+    def _enter_stage_two(self):
+        self.release_capture()
+        self._trainable = trainable_flat_ranges(self.shapes, self._frozen_prefixes())
+        self._slots_folded = False
+        self._stage_two_options()
+
+    def _stage_two_options(self):
+        """Launch options of the stage-two step, re-derived for its own launches (subclasses)."""
+
+    def _stage_two_packs(self) -> list:
+        """The modules whose packed operand copies a stage-two update rebuilds: the fusion tower."""
+        return [self.t_fus]
+
+    def _pass_weights(self, training: bool) -> torch.Tensor:
+        """The device table of loss coefficients the heads launch of this pass reads."""
+        return self._stage_group["weights"] if (training and self._frozen) else self.loss_weights
+
+    def _stage_two_total(self, training: bool):
+        """Stage two, training: losses[3] = losses[2].  The heads kernel adds each workgroup's term to its head's loss and,
+        times the coefficient, to the total with two atomics; with coefficients (0, 0, 1) the total is the same terms, but three
+        or more workgroups may arrive in another order at the second address -- one 4-byte copy makes the equality exact."""
+        if training and self._frozen:
+            self.losses[3:4].copy_(self.losses[2:3])
+
+    def _update_stage_two(self, grad_scale: float, grad_bf16):
+        if grad_bf16 is not None:
+            raise RuntimeError("stage two (freeze_modalities) is single GPU: no exchanged bf16 gradient")
+        self._slots_folded = False
+        for lo, hi in self._trainable:               # the existing range form, one launch per trainable range
+            self._adam_chunk(lo, hi, grad_scale)
+        for m in self._stage_two_packs():
+            m.pack(force=True)
+
+    def _refuse_exchange_when_frozen(self, grad_sync):
+        if grad_sync is not None and self._frozen:
+            raise RuntimeError("stage two (freeze_modalities) is single GPU: a grad_sync is refused")
+
     # ---- optimizer -------------------------------------------------------------------------------------------
     def _check_grad_bf16(self, grad_bf16: Optional[torch.Tensor]):
         if grad_bf16 is not None and (grad_bf16.dtype != torch.bfloat16 or grad_bf16.numel() != self.n_params or not grad_bf16.is_cuda):
@@ -752,7 +913,9 @@ class _FlatEngine:
         zero on entry: it is cleared at construction and again by every optimizer_step (the Adam kernel clears
         each element it consumes), so no separate fill pass is needed.  (Channel-mixing weight gradients of the
         overwriting towers -- _setup_wgrad -- are written, not added: those ranges need no clearing.)  On return flat_g
-        holds the complete gradient: a row group the weight-gradient launch left in a slot is folded in here."""
+        holds the complete gradient: a row group the weight-gradient launch left in a slot is folded in here.
+        After freeze_modalities() flat_g is UNSPECIFIED inside the frozen keys' ranges (no backward of a frozen tower runs, what
+        stage one left there is neither cleared nor consumed); inside the trainable ranges it is the gradient of loss_fusion."""
         self._step(batch, fused_update=False)
         for t in self._slot_towers:
             t.wgrad_fold()
@@ -848,6 +1011,9 @@ class _FlatEngine:
     def _update(self, grad_scale: float = 1.0, grad_bf16: Optional[torch.Tensor] = None):
         """Adam over every parameter + operand re-pack.  One launch (m2m_adam_pack_all) where the model allows it: the
         re-pack then takes the updated weights from the workgroup that computed them instead of re-reading the masters."""
+        if self._frozen:
+            self._update_stage_two(grad_scale, grad_bf16)
+            return
         mods = self._adam_pack_modules() if self._fused_update else None
         # the slot of a two-group tower: added inside Adam (fused step) unless forward_backward has folded it in already
         ranges = self._ranges_keep if (self._slots_folded or grad_bf16 is not None) else self._ranges_add
@@ -880,6 +1046,7 @@ class _FlatEngine:
         exchange (the whole step when there is none); update(k, scale): the update behind the exchange -- of chunk k of
         _update_chunks() when pipelined (chunk k + 1 .. are still on the communication stream), else k = 0: everything.
         Eager steps pass _phases(), a captured step its graphs' replays."""
+        self._refuse_exchange_when_frozen(grad_sync)
         mode = _exchange_mode(grad_sync)
         first()
         if mode == "none":
@@ -949,6 +1116,7 @@ class _FlatEngine:
         capture() does not train: the warm-up steps it needs are undone (parameters, Adam moments, step counters)."""
         if steps < 1 or (steps > 1 and grad_sync is not None):
             raise ValueError("steps > 1 is only supported without a gradient exchange")
+        self._refuse_exchange_when_frozen(grad_sync)
         nb = len(batch)
         slots = [tuple(t.clone() for t in batch) for _ in range(steps)]
         if steps > 1 and config.switch_on("M2M_CAPTURE_SHARE_SLOTS"):
@@ -1048,6 +1216,8 @@ class _FlatEngine:
 
         # as capture(): the warm-up runs REAL steps; everything they change is put back -- here the feed's state too
         state = [self.flat_p, self.flat_m, self.flat_v, self.flat_g, self.adam_state, self.drop_step, feed.state, feed._acc]
+        if feed.mute_state is not None:
+            state.append(feed.mute_state)            # (the warm-up gathers advance the muting schedule's step index too)
         if self.scores is not None:
             state.append(self.scores.table)
         if self.rank is not None:
@@ -1295,7 +1465,8 @@ class _TwoTowerEngine(_FlatEngine):
         so = 0                                               # host step offset of this pass's launches (see _embed_fold)
         pa, pb, pf = (None, None, None) if self._heads_pool else (self.pool_a, self.pool_b, self.pool_fus)
         self._pending_bump = False
-        if self._embed_fold and training and prologue:
+        self._step_weights = self._pass_weights(training)
+        if self._embed_fold and training and prologue and not self._frozen:      # (stage two: the plain head of the step)
             # both patch embeddings inside the two-tower launch; head of the step: losses = 0, Adam step += 1 in that launch,
             # the dropout counter advances in the weight-gradient launch of _backward (every launch in between gets step = 1)
             so, self._pending_bump = 1, True
@@ -1343,7 +1514,8 @@ class _TwoTowerEngine(_FlatEngine):
             heads[1]["tokens"] = (b_part.data_ptr(), self.Nb, sb_)
             heads[2]["tokens"] = (self.fus_out, self.Nf, fs)
         self._wgrad_heads = None
-        if training and with_grad and self._head_part is not None:
+        if training and with_grad and self._head_part is not None and not self._frozen:
+            # (stage two: its single-tower weight-gradient call adds no slots; the heads add with atomics)
             for i, h in enumerate(heads):
                 h["g_part"] = self._head_part[i]
             self._wgrad_heads = heads                     # _backward's weight-gradient launch adds the slots to g_w / g_b
@@ -1352,6 +1524,7 @@ class _TwoTowerEngine(_FlatEngine):
         if training and with_grad and self._fused_heads:
             return                                         # heads + losses ride in the fusion tower's backward launch (_backward)
         self._loss_heads(heads, labels, not training)      # a training step's _prologue already cleared the losses
+        self._stage_two_total(training)
 
     def _backward(self, xa, xb, fused_update: bool = False):
         """Backward of the whole model.  fused_update: also apply Adam + re-pack (single-GPU path; with a gradient
@@ -1359,6 +1532,16 @@ class _TwoTowerEngine(_FlatEngine):
         B, D = self.B, self.D
         fs = self.Nf * D
         sd = self.drop_step
+        if self._frozen:
+            # stage two: nothing behind the fusion function trains.  The fusion tower's backward, a non-concat fusion's own
+            # backward (a gated unit's weight gradients are trainable), the fusion tower's weight gradients as a single-tower
+            # call, Adam over the trainable ranges, the fusion tower's re-pack -- all on the main stream.
+            self.t_fus.backward(B, None, 0, self.dpool_fus, self.d_fused, fs, self.seed, 0, sd)
+            self._fusion_backward()
+            self.t_fus.wgrad(B, self.seed, 0, sd)
+            if fused_update:
+                self._update(1.0)
+            return
         a, b = self.MODS
         so = 1 if self._pending_bump else 0                 # (the forward of this step left the dropout counter un-advanced)
         if self._fused_heads:
@@ -1416,6 +1599,12 @@ class _TwoTowerEngine(_FlatEngine):
         if fused_update:
             self._update(1.0)
 
+    def _stage_two_options(self):
+        """The options _setup_wgrad chose for the grouped weight-gradient launch (the fusion tower's slot, overwrite decided with
+        the slot in hand, the embeddings' kept ranges) re-derived for the single-tower call of stage two."""
+        self.t_fus.set_wgrad_overwrite(False)
+        self._setup_wgrad([[self.t_fus]])
+
     def _update_chunks(self):
         """One chunk per parameter segment, in flat order: modality a (its patch embedding + tower), modality b, fusion tower
         + the three heads (heads have no packed copies)."""
@@ -1468,7 +1657,7 @@ class AVMnistEngine(_TwoTowerEngine):
 
     def _loss_heads(self, heads, labels, zero_losses):
         heads_ce(heads, labels, self.B, self.D, self.K, out=(self.logits, self.losses, self.preds), zero_losses=zero_losses,
-                 weights=self.loss_weights)
+                 weights=self._step_weights)
 
     def _heads_are_ce(self) -> bool:
         return True
@@ -1517,7 +1706,7 @@ class AVMnistUQEngine(AVMnistEngine):
         # (self.preds at call time: a multi-step capture points it at its per-step slots)
         heads_edl(heads, labels, self.B, self.D, self.K,
                   out=(self.logits, self.losses, self.preds, self.uncertainty, self.preds[2]), zero_losses=zero_losses,
-                  weights=self.loss_weights)
+                  weights=self._step_weights)
 
     def _heads_are_ce(self) -> bool:
         return False                                          # no fused heads + fusion-backward launch: that one computes cross-entropy
@@ -1577,7 +1766,7 @@ class MMIMDBEngine(_TwoTowerEngine):
 
     def _loss_heads(self, heads, labels, zero_losses):
         heads_bce(heads, labels, self.pos_weight, self.B, self.D, self.K, out=(self.logits, self.losses, self.preds),
-                  zero_losses=zero_losses, weights=self.loss_weights)
+                  zero_losses=zero_losses, weights=self._step_weights)
 
 
 class MimicEngine(_FlatEngine):
@@ -1689,13 +1878,21 @@ class MimicEngine(_FlatEngine):
             heads[1]["tokens"] = (time_part.data_ptr(), self.Nt, fs)
             heads[2]["tokens"] = (self.fus_out, self.Nf, fs)
         heads_ce(heads, labels, B, D, self.K, out=(self.logits, self.losses, self.preds), zero_losses=not training,
-                 weights=self.loss_weights)
+                 weights=self._pass_weights(training))
+        self._stage_two_total(training)
 
     def _backward(self, static, time, fused_update: bool = False):
         B, D = self.B, self.D
         fs = self.Nf * D
         sd = self.drop_step
         self.t_fus.backward(B, None, 0, self.dpool_fus, self.d_fused, fs, self.seed, 0, sd)
+        if self._frozen:
+            # stage two: the time tower's backward, the static MLP's (riding or not) and the projection's weight gradient are
+            # skipped -- the existing single-tower forms cover what is left, on the main stream at any batch size
+            self.t_fus.wgrad(B, self.seed, 0, sd)
+            if fused_update:
+                self._update(1.0)
+            return
         d_time_part = self.d_fused.view(-1)[D:]
         if not (self._conc_bwd and self.concurrent) and self._merged_tail:
             # one stream (small batch): both towers' weight gradients in ONE launch, ONE Adam over the flat buffer, ONE re-pack

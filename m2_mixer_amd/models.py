@@ -94,6 +94,17 @@ def _plain(c) -> dict:
     return {k: (_plain(v) if isinstance(v, dict) else v) for k, v in dict(c).items()}
 
 
+def muting_codes(steps: int, muting_probs, mods: Sequence[str], rng=np.random) -> np.ndarray:
+    """The muting schedule of `steps` stage-two training steps as the codes engine.EpochFeed takes: `steps` calls of
+    rng.choice([a, b, "multimodal"], p=...) in order -- shared_step's draw (models/avmnist.py:243-251), one per training step, so
+    the generator is consumed exactly as a loop of training steps consumes it -- mapped to 0 ("multimodal": mute nothing), 1 (mute
+    modality a, the feed's source 0) and 2 (modality b, source 1)."""
+    names = list(mods) + ["multimodal"]
+    code = {names[0]: 1, names[1]: 2, "multimodal": 0}
+    p = [muting_probs[n] for n in names]
+    return np.asarray([code[str(rng.choice(names, p=p))] for _ in range(int(steps))], dtype=np.int32)
+
+
 class EngineOptimizer(torch.optim.Optimizer):
     """The optimizer of a module bound to a fused engine (_MultiLossModule.bind_engine): the engine's Adam, which every replayed
     training step has already applied.  step() / zero_grad() are no-ops (a LightningModule subclass sets
@@ -158,6 +169,7 @@ class _MultiLossModule(nn.Module):
         self.current_epoch = 0                       # a trainer sets it (Lightning property in the reference)
         self.dropout = self.model_cfg.get("dropout", 0.0)
         self._engine = None                          # bind_engine: the fused engine whose buffers hold this module's parameters
+        self._two_stage = False                      # bind_engine(..., two_stage=True): the bound engine follows the freeze epoch
         self._engine_optimizer: Optional[EngineOptimizer] = None     # the latest configure_optimizers() of a bound module
 
     # ---- pieces shared by the three tasks ----------------------------------------------------------------
@@ -194,6 +206,10 @@ class _MultiLossModule(nn.Module):
                 for p in mod.parameters():
                     p.requires_grad = False
         self.modalities_freezed = True
+        if self._engine is not None and self._two_stage:
+            # bound: the engine family enters stage two; its captured graph is gone, the next full batch captures stage two's
+            self._engine.freeze_modalities()
+            self._replay = None
 
     # ---- checkpoint I/O ------------------------------------------------------------
     checkpoint_path: Optional[str] = None
@@ -292,15 +308,20 @@ class _MultiLossModule(nn.Module):
         return self._engine
 
     def bind_engine(self, batch_size: int, precision: Optional[str] = None, scores: bool = False, rank_scores: bool = False,
-                    rank_capacity: int = 65536):
+                    rank_capacity: int = 65536, two_stage: bool = False):
         """Engine-backed mode: build the fused engine (engine.py) for `batch_size`, copy this module's weights into it, then
         point every parameter's `.data` at the engine's buffer (`engine.params[key]`): the Parameter objects stay the same,
         `parameters()`, `state_dict()`, `save_checkpoint()` read the live weights, and no copy is taken again.  From then on
         training_step replays the engine's captured step, validation_step / test_step run its evaluation, configure_optimizers
         returns an EngineOptimizer and validation_epoch_end forwards the loss-weight schedule to the engine.
         A LightningModule subclass sets `automatic_optimization = False` when bound: the replayed step already updated the
-        weights (EngineOptimizer.step is a no-op).  Refused: epoch-triggered freezing and random muting (the engine trains every
-        parameter and has no muting); a fixed `mute` is supported.
+        weights (EngineOptimizer.step is a no-op).  Refused by default: epoch-triggered freezing and random muting; a fixed `mute`
+        is supported.
+        two_stage=True accepts `freeze_modalities_on_epoch` and `random_modality_muting_on_freeze`: training_step then runs the
+        reference's draw and freeze first (_maybe_freeze_and_mute); at the freeze epoch the engine enters stage two
+        (engine.freeze_modalities: loss_fusion alone, the modality towers and their heads untouched, their backward skipped) and
+        the next full batch captures the stage-two graph; the per-step draw reaches the engine as a zeroed input.  A module
+        already frozen when bound freezes its engine at once.
         scores=True: training_step / validation_step / test_step also add their batch's counts into the train / val / test count
         tables on the device (the reference's three setup_scores dictionaries; one small launch per step, inside the captured
         graph for training), and training_epoch_end / validation_epoch_end / test_epoch_end return the reference's scores.
@@ -312,10 +333,11 @@ class _MultiLossModule(nn.Module):
         their own with scores=False.  Off (the default): no buffer, no launch."""
         if self._engine is not None:
             raise RuntimeError("bind_engine: this module is already bound to an engine")
-        if self.freeze_modalities_on_epoch is not None or self.modalities_freezed:
-            raise NotImplementedError("bind_engine: freeze_modalities_on_epoch -- the fused engine trains every parameter")
-        if self.random_modality_muting_on_freeze:
-            raise NotImplementedError("bind_engine: random_modality_muting_on_freeze -- the fused engine has no random muting")
+        if not two_stage:
+            if self.freeze_modalities_on_epoch is not None or self.modalities_freezed:
+                raise NotImplementedError("bind_engine: freeze_modalities_on_epoch -- the fused engine trains every parameter")
+            if self.random_modality_muting_on_freeze:
+                raise NotImplementedError("bind_engine: random_modality_muting_on_freeze -- the fused engine has no random muting")
         dev = next(self.parameters()).device
         if dev.type != "cuda":
             raise RuntimeError("bind_engine: the module must be on the GPU (.to('cuda')) first; the engine has no CPU path")
@@ -327,6 +349,9 @@ class _MultiLossModule(nn.Module):
                 p.data = eng.params[k]
         self._bind_buffers(eng)
         self._engine = eng
+        self._two_stage = bool(two_stage)
+        if self._two_stage and self.modalities_freezed:
+            eng.freeze_modalities()
         self._replay = None
         self._train_siblings: Dict[int, Any] = {}
         self._eval_siblings: Dict[int, Any] = {}
@@ -423,7 +448,9 @@ class _MultiLossModule(nn.Module):
         eng = self._engine
         if eng is None:
             return self.shared_step(batch, mode="train")
-        if self.modalities_freezed:
+        if self._two_stage:
+            self._maybe_freeze_and_mute("train")     # the reference's freeze at its epoch and the per-step draw (self.mute)
+        elif self.modalities_freezed:
             raise NotImplementedError("a bound module trains every parameter: freezing is not supported")
         xa, xb, labels = self._engine_batch(batch, train=True)
         if self._engine_optimizer is not None:
@@ -778,6 +805,12 @@ class MimicMixerMultiLoss(_MultiLossModule):
 
     def _engine_batch(self, batch, train):
         static, time, labels = batch
+        # bound two-stage: stage two's per-step draw (the reference's MIMIC shared_step itself never mutes: a fixed `mute` key
+        # stays without effect, bound or not)
+        if train and self._two_stage and self.mute == "static":
+            static = torch.zeros_like(static)
+        elif train and self._two_stage and self.mute == "time":
+            time = torch.zeros_like(time)
         return static.float(), time.float(), labels.long()
 
     def _engine_preds(self, preds, logits):
