@@ -252,7 +252,7 @@ def feed_plan(n: int, batch_size: int, steps: int, drop_last: bool = False) -> T
 
 
 def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = True, tail_engine=None, drop_last: bool = False,
-                  order=None, split: str = "train", muting=None) -> Dict[str, float]:
+                  order=None, split: str = "train", muting=None, probe: bool = False) -> Dict[str, float]:
     """run_epoch with the batches fetched on the device (engine.EpochFeed): one pass over the first `n`
     samples (default: all) of `order` (an index tensor for feed.start; None: the split's own order), every sample exactly once,
     in order.  Any of the engines; single GPU.
@@ -263,6 +263,9 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
     must exist before the capture -- prepare_tail_engine's rule -- or engine.sibling(tail)), fed by gather_into, with pack()
     before and after, as run_epoch does.  Nothing is read back until the end.
     train=False: `replay` is unused (None); every batch is gathered eagerly, evaluated and accumulated.
+    probe=True (with train=False): engine.probe in place of engine.evaluate -- the training-mode forward (dropout on, the stage's
+    training coefficients) that updates nothing: GradBlend's loss sums (modules/gradblend.py:43-60).  Score tables and ranking
+    buffers are not fed by a probing pass.
     muting (train=True, a feed built with muting=True): the epoch's muting codes, one per training step (models.muting_codes),
     handed to feed.start; evaluation never mutes (its schedule is all zeros).
 
@@ -287,6 +290,8 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
     feed.bind(engine)
     if muting is not None and not train:
         raise ValueError("run_epoch_fed: evaluation never mutes (muting= goes with train=True)")
+    if probe and train:
+        raise ValueError("run_epoch_fed: probe=True goes with train=False (a probing pass updates nothing)")
     feed.start(order, muting=muting)
     steps = replay.steps if train else 1
     replays, singles, tail = feed_plan(n, B, steps, drop_last)
@@ -304,7 +309,10 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
         slots = feed.new_slots()
         for _ in range(replays * steps + singles):
             feed.gather_into(slots)
-            engine.evaluate(*slots, **extra)
+            if probe:
+                engine.probe(*slots)
+            else:
+                engine.evaluate(*slots, **extra)
             feed.accumulate(engine, slots[-1])
     if tail:
         if tail_engine is None:
@@ -319,6 +327,8 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
         if train:
             tail_engine.train_step(*tslots)
             engine.pack()                                          # the tail step changed the weights
+        elif probe:
+            tail_engine.probe(*tslots)
         else:
             tail_engine.evaluate(*tslots, **extra)
         feed.accumulate(tail_engine, tslots[-1])

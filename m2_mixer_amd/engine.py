@@ -24,7 +24,10 @@ What changes relative to the module path (modules/mixer.py + torch autograd):
   * freeze_modalities(): stage two of the reference's two-stage training (models/avmnist.py:292-293, :314-324) -- the loss is
     loss_fusion alone, the modality towers, their embeddings and heads are never written again, and the step skips their
     backward, weight gradients, Adam and re-pack; EpochFeed(muting=True) zeroes one input per step from
-    a schedule on the device (csrc/feed.hip: m2m_feed_gather_muted).
+    a schedule on the device (csrc/feed.hip: m2m_feed_gather_muted);
+  * train_modalities_only(): the mirror image -- the loss is loss_a + loss_b, no fusion function or fusion tower runs, the fusion
+    keys are never written (the unimodal models of Gradient-Blending); clone() and probe() are the other two pieces
+    gradblend.GradBlend is built from.
 """
 from __future__ import annotations
 
@@ -152,11 +155,13 @@ def mimic_param_shapes(cfg: dict) -> "OrderedDict[str, tuple]":
     return s
 
 
-def trainable_flat_ranges(shapes: "Dict[str, tuple]", frozen_prefixes: Sequence[str]) -> List[Tuple[int, int]]:
+def trainable_flat_ranges(shapes: "Dict[str, tuple]", frozen_prefixes: Sequence[str], invert: bool = False) -> List[Tuple[int, int]]:
     """Stage two of the reference's two-stage training (models/avmnist.py:314-324): the contiguous flat ranges [lo, hi) of the
     parameters that keep training, given the ordered state-dict shapes and the key prefixes that freeze.  Neighbouring trainable
     parameters are merged; the ranges are sorted and disjoint, and with the frozen keys' ranges they tile [0, n_params).  Pure:
-    no device, no library."""
+    no device, no library.
+    invert=True: the complement -- the ranges of the keys that DO start with one of the prefixes (the modalities-only stage
+    trains exactly what stage two freezes: train_modalities_only)."""
     frozen = tuple(frozen_prefixes)
     out: List[Tuple[int, int]] = []
     off = 0
@@ -164,7 +169,7 @@ def trainable_flat_ranges(shapes: "Dict[str, tuple]", frozen_prefixes: Sequence[
         cnt = 1
         for d in shp:
             cnt *= int(d)
-        if not k.startswith(frozen):
+        if k.startswith(frozen) == invert:
             if out and out[-1][1] == off:
                 out[-1] = (out[-1][0], off + cnt)
             else:
@@ -545,8 +550,9 @@ class _FlatEngine:
             # graph follows set_fusion_loss_weight / set_loss_weights without being captured again
             self.loss_weights = torch.tensor(self._head_weight_list(), dtype=torch.float32, device=dev)
             self._loss_weight_group = {"fused_heads": False}      # (shared by the siblings, like the table itself)
-            # the training stage of the engine family (freeze_modalities): shared by existing and later siblings
-            self._stage_group = {"frozen": False, "weights": None, "members": []}
+            # the training stage of the engine family (freeze_modalities: "frozen", train_modalities_only: "modal"): shared by
+            # existing and later siblings
+            self._stage_group = {"frozen": False, "modal": False, "weights": None, "members": []}
         self.seed = (share.seed if share is not None else seed) & 0xFFFFFFFF
         # scores=True: every training step ends its forward with one launch that adds the batch's counts into `self.scores`
         # (a sibling adds into its parent's table); off: no table, no launch -- the step is exactly the one without the feature
@@ -580,6 +586,7 @@ class _FlatEngine:
         self._embeds: List[EmbedRuntime] = []
         self._fused_heads = False                       # the heads ride in the fusion tower's backward launch (_TwoTowerEngine)
         self._eval_only = False                         # sibling(..., trains=False)
+        self._probing = False                           # inside probe(): the step head leaves the Adam count alone
         self._tail_engines: Dict[int, "_FlatEngine"] = {}     # training siblings of ragged last batches (data.run_epoch)
         # side streams for the paths whose towers cannot share a launch (wide towers, mixed shapes, the MIMIC static MLP): the
         # second modality runs beside the first.  The AV-MNIST step needs none of them: nine launches on the main stream.
@@ -587,7 +594,8 @@ class _FlatEngine:
         self.s_fus = torch.cuda.Stream(device=dev)
         self.s_emb = torch.cuda.Stream(device=dev)
         self.concurrent = config.switch_on("M2M_CONCURRENT")      # 0: every launch on the main stream (A/B)
-        # the loss coefficients the heads launch of the current pass reads: loss_weights, or stage two's (0, 0, 1) in training
+        # the loss coefficients the heads launch of the current pass reads: loss_weights, or in training stage two's (0, 0, 1) /
+        # the modalities-only stage's (1, 1)
         self._step_weights = self.loss_weights
         self._trainable: List[Tuple[int, int]] = []      # stage two: the flat ranges Adam still updates (trainable_flat_ranges)
         self._build()
@@ -596,6 +604,8 @@ class _FlatEngine:
         self._stage_group["members"].append(weakref.ref(self))
         if self._frozen:
             self._enter_stage_two()                  # a sibling built after freeze_modalities()
+        if self._modal:
+            self._enter_modal_stage()                # ... after train_modalities_only()
         self.pack()
 
     # ---- helpers for subclasses ----------------------------------------------------------------------------
@@ -823,20 +833,29 @@ class _FlatEngine:
         grp = self._stage_group
         if grp["frozen"]:
             return
+        if grp["modal"]:
+            raise RuntimeError("freeze_modalities: this engine family is in the modalities-only stage (train_modalities_only), "
+                               "which has no way back")
         if self._loss_weight_group["fused_heads"]:
             raise RuntimeError("freeze_modalities: the fused heads + fusion backward launch (M2M_FUSED_HEADS=1) takes the loss "
                                "weights by value; stage two needs that switch off")
         grp["weights"] = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float32, device=self.device)
         grp["frozen"] = True
+        self._enter_stage(lambda m: m._enter_stage_two())
+
+    def _enter_stage(self, enter):
+        """What freeze_modalities and train_modalities_only share once the stage group is marked: clear the new stage's trainable
+        gradient ranges, let every member re-derive its launch options (enter(member)), narrow the kept gradient ranges."""
+        grp = self._stage_group
         members = [m for m in (r() for r in grp["members"]) if m is not None]
         grp["members"] = [weakref.ref(m) for m in members]
-        # Stage one left the ranges its overwriting weight-gradient launch owned uncleared ("keep").  A range stage two's
-        # single-tower call accumulates into instead (another row plan: no slot) must start from zero: clear every trainable range
-        # once, here, outside any graph.
-        for lo, hi in trainable_flat_ranges(self.shapes, self._frozen_prefixes()):
+        # Stage one left the ranges its overwriting weight-gradient launch owned uncleared ("keep").  A range the new stage's
+        # weight-gradient call accumulates into instead (another row plan: no slot) must start from zero: clear every trainable
+        # range once, here, outside any graph.
+        for lo, hi in trainable_flat_ranges(self.shapes, self._frozen_prefixes(), invert=grp["modal"]):
             self.flat_g[lo:hi].zero_()
         for m in members:
-            m._enter_stage_two()
+            enter(m)
         # one gradient buffer: a range one engine leaves uncleared must be overwritten by every other training engine (sibling())
         trains = [m for m in members if not m._eval_only]
         for m in trains:
@@ -856,9 +875,71 @@ class _FlatEngine:
         """The modules whose packed operand copies a stage-two update rebuilds: the fusion tower."""
         return [self.t_fus]
 
+    # ---- the modalities-only stage: the unimodal models of Gradient-Blending (modules/gradblend.py:92-98) ----------------------
+    @property
+    def _modal(self) -> bool:
+        return self._stage_group["modal"]
+
+    @property
+    def _staged(self) -> bool:
+        """In stage two or in the modalities-only stage: Adam runs per trainable range, a gradient exchange is refused."""
+        return self._stage_group["frozen"] or self._stage_group["modal"]
+
+    def train_modalities_only(self):
+        """Enter the mirror image of stage two, for this engine, its siblings and siblings built later (one-way, like the freeze):
+        the two unimodal models of Gradient-Blending (modules/gradblend.py:92-98: each modality tower with its own head) trained
+        at once -- they share no parameter and Adam is element-wise, so this is the reference's two separate trainings.  From the
+        next training step on
+          * the training loss is loss_a + loss_b, coefficients (1, 1): the heads launch takes the two modality heads only;
+            losses[0..1] are their losses, losses[2] == 0, losses[3] == losses[0] + losses[1].  logits[2] / preds[2] keep what
+            the last full forward left there;
+          * the step runs no fusion function and no fusion tower, forward or backward: the modality towers' backward starts from
+            their heads' d_pooled alone (d_out NULL);
+          * the fusion function's and the fusion tower's parameters, classifier_fusion and both of their Adam moments are never
+            written again; Adam runs over the complement of stage two's ranges, the re-pack over the modality towers and their
+            embeddings.
+        evaluate() stays the full model under `loss_weights`.  Captured graphs are dropped: capture again.  Refused with
+        M2M_FUSED_HEADS=1, on engines built with scores / rank_scores (the fusion head's predictions are not produced), after
+        freeze_modalities(); a gradient exchange is refused in this stage (single GPU)."""
+        grp = self._stage_group
+        if grp["modal"]:
+            return
+        if grp["frozen"]:
+            raise RuntimeError("train_modalities_only: this engine family is in stage two (freeze_modalities), which has no way back")
+        if self._loss_weight_group["fused_heads"]:
+            raise RuntimeError("train_modalities_only: the fused heads + fusion backward launch (M2M_FUSED_HEADS=1) belongs to the "
+                               "fusion tower's backward, which this stage does not run; it needs that switch off")
+        if self.scores is not None or self.rank is not None:
+            raise RuntimeError("train_modalities_only: an engine built with scores=True / rank_scores=True counts the fusion head's "
+                               "predictions on every training step; this stage does not produce them")
+        grp["weights"] = torch.tensor([1.0, 1.0, 0.0], dtype=torch.float32, device=self.device)
+        grp["modal"] = True
+        self._enter_stage(lambda m: m._enter_modal_stage())
+
+    def _enter_modal_stage(self):
+        self.release_capture()
+        self._trainable = trainable_flat_ranges(self.shapes, self._frozen_prefixes(), invert=True)
+        self._slots_folded = False
+        self._modal_stage_options()
+
+    def _modal_stage_options(self):
+        """Launch options of the modalities-only step, re-derived for its own launches (subclasses)."""
+
+    def _modal_stage_packs(self) -> list:
+        """The modules whose packed operand copies a modalities-only update rebuilds."""
+        raise NotImplementedError
+
+    def _modal_total(self, training: bool):
+        """Modalities-only stage, training: the two-head launch left its total in losses[2] (slot nheads).  losses[3] is written
+        as the one fp32 sum of the two heads' losses (the atomics' arrival order does not show), losses[2] is the fusion head's
+        loss, which this stage does not compute: zero."""
+        if training and self._modal:
+            torch.add(self.losses[0:1], self.losses[1:2], out=self.losses[3:4])
+            self.losses[2:3].copy_(self._stage_group["weights"][2:3])
+
     def _pass_weights(self, training: bool) -> torch.Tensor:
         """The device table of loss coefficients the heads launch of this pass reads."""
-        return self._stage_group["weights"] if (training and self._frozen) else self.loss_weights
+        return self._stage_group["weights"] if (training and self._staged) else self.loss_weights
 
     def _stage_two_total(self, training: bool):
         """Stage two, training: losses[3] = losses[2].  The heads kernel adds each workgroup's term to its head's loss and,
@@ -869,16 +950,21 @@ class _FlatEngine:
 
     def _update_stage_two(self, grad_scale: float, grad_bf16):
         if grad_bf16 is not None:
-            raise RuntimeError("stage two (freeze_modalities) is single GPU: no exchanged bf16 gradient")
+            raise RuntimeError("stage two (freeze_modalities) / the modalities-only stage is single GPU: no exchanged bf16 gradient")
+        if not self._slots_folded:                   # (stage two's single-tower call has no slot; a grouped modality pair may)
+            for t in self._slot_towers:
+                t.wgrad_fold()
         self._slots_folded = False
         for lo, hi in self._trainable:               # the existing range form, one launch per trainable range
             self._adam_chunk(lo, hi, grad_scale)
-        for m in self._stage_two_packs():
+        for m in (self._modal_stage_packs() if self._modal else self._stage_two_packs()):
             m.pack(force=True)
 
     def _refuse_exchange_when_frozen(self, grad_sync):
         if grad_sync is not None and self._frozen:
             raise RuntimeError("stage two (freeze_modalities) is single GPU: a grad_sync is refused")
+        if grad_sync is not None and self._modal:
+            raise RuntimeError("the modalities-only stage (train_modalities_only) is single GPU: a grad_sync is refused")
 
     # ---- optimizer -------------------------------------------------------------------------------------------
     def _check_grad_bf16(self, grad_bf16: Optional[torch.Tensor]):
@@ -905,8 +991,40 @@ class _FlatEngine:
 
     def _prologue(self):
         """Head of a training step: Adam step count += 1, dropout counter += 1, losses = 0 -- one tiny launch."""
-        L.check(L.lib().m2m_step_prologue(self.adam_state.data_ptr(), self.drop_step.data_ptr(), self.losses.data_ptr(), 4,
+        L.check(L.lib().m2m_step_prologue(L.ptr(self._head_adam()), self.drop_step.data_ptr(), self.losses.data_ptr(), 4,
                                           L.stream_ptr()), "step_prologue")
+
+    def _head_adam(self) -> Optional[torch.Tensor]:
+        """The Adam state the head of this pass advances: none under probe() (the prologue forms take NULL)."""
+        return None if self._probing else self.adam_state
+
+    @torch.no_grad()
+    def probe(self, *batch):
+        """The training-mode forward alone (GradBlend's get_loss, modules/gradblend.py:43-60: modules in train mode, nothing
+        updated): dropout on, the dropout counter advanced as a training step advances it, `losses` / `logits` / `preds` filled
+        under the stage's training coefficients -- and no gradient, parameter, moment or Adam count written.  Returns `losses`."""
+        self._probing = True
+        try:
+            self._forward(*batch, training=True, with_grad=False, prologue=True)
+        finally:
+            self._probing = False
+        return self.losses
+
+    def clone(self, batch_size: Optional[int] = None):
+        """An INDEPENDENT engine of the same cfg, precision and hyper-parameters (default: the same batch size) that starts from a
+        copy of this one's parameters and loss weights, with zero Adam moments, step count and dropout counter, in stage one, and
+        without score tables or ranking buffers.  Nothing is shared with this engine (unlike sibling())."""
+        prec = {v: k for k, v in L.PREC_BY_NAME.items() if k in ("bf16", "fp32")}[self.prec]
+        new = type(self)(self.cfg, self.B if batch_size is None else int(batch_size), device=self.device, precision=prec,
+                         lr=float(self.adam_state[1]), betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, seed=self.seed,
+                         init=False, **self._sibling_kwargs())
+        new.flat_p.copy_(self.flat_p)
+        new.loss_weights.copy_(self.loss_weights)
+        new.head_weights = dict(self.head_weights)
+        if hasattr(self, "pos_weight"):
+            new.pos_weight.copy_(self.pos_weight)
+        new.pack()
+        return new
 
     def forward_backward(self, *batch):
         """forward (dropout on) -> multi-head loss -> backward; gradients are ADDED into flat_g, which must be
@@ -1011,7 +1129,7 @@ class _FlatEngine:
     def _update(self, grad_scale: float = 1.0, grad_bf16: Optional[torch.Tensor] = None):
         """Adam over every parameter + operand re-pack.  One launch (m2m_adam_pack_all) where the model allows it: the
         re-pack then takes the updated weights from the workgroup that computed them instead of re-reading the masters."""
-        if self._frozen:
+        if self._staged:
             self._update_stage_two(grad_scale, grad_bf16)
             return
         mods = self._adam_pack_modules() if self._fused_update else None
@@ -1466,7 +1584,7 @@ class _TwoTowerEngine(_FlatEngine):
         pa, pb, pf = (None, None, None) if self._heads_pool else (self.pool_a, self.pool_b, self.pool_fus)
         self._pending_bump = False
         self._step_weights = self._pass_weights(training)
-        if self._embed_fold and training and prologue and not self._frozen:      # (stage two: the plain head of the step)
+        if self._embed_fold and training and prologue and not self._staged and not self._probing:      # (a stage: the plain head of the step)
             # both patch embeddings inside the two-tower launch; head of the step: losses = 0, Adam step += 1 in that launch,
             # the dropout counter advances in the weight-gradient launch of _backward (every launch in between gets step = 1)
             so, self._pending_bump = 1, True
@@ -1480,7 +1598,7 @@ class _TwoTowerEngine(_FlatEngine):
             sa, sb = self.x0_splits
             if can_group_embeds(self.e_a, self.e_b):
                 # the step prologue (counters, losses = 0) rides in this launch, the first one of the step
-                head = (self.adam_state, self.drop_step, self.losses) if prologue else None
+                head = (self._head_adam(), self.drop_step, self.losses) if prologue else None
                 embeds_forward([self.e_a, self.e_b], [xa, xb], [self._x0_a, self._x0_b], B, [sa, sb], head)
             else:
                 if prologue:
@@ -1502,8 +1620,10 @@ class _TwoTowerEngine(_FlatEngine):
             self.e_a.forward(xa, B, self.x0_a)
             self.t_a.forward(self.x0_a, self.Na * D, B, out_a, sa_, pa, training, self.seed, 0, sd)
             main.wait_stream(side)
-        self._fusion_forward(training and with_grad)
-        self.t_fus.forward(self.fused, fs, B, self.fus_out, fs, pf, training, self.seed, so, sd)
+        modal = training and self._modal                    # the modalities-only stage: no fusion function, no fusion tower
+        if not modal:
+            self._fusion_forward(training and with_grad)
+            self.t_fus.forward(self.fused, fs, B, self.fus_out, fs, pf, training, self.seed, so, sd)
         a, b = self.MODS
         hw = self.head_weights
         heads = [self._head(a, self.pool_a, self.dpool_a, hw[a], with_grad),
@@ -1514,8 +1634,10 @@ class _TwoTowerEngine(_FlatEngine):
             heads[1]["tokens"] = (b_part.data_ptr(), self.Nb, sb_)
             heads[2]["tokens"] = (self.fus_out, self.Nf, fs)
         self._wgrad_heads = None
-        if training and with_grad and self._head_part is not None and not self._frozen:
-            # (stage two: its single-tower weight-gradient call adds no slots; the heads add with atomics)
+        if modal:
+            heads = heads[:2]                              # (their total lands in losses[2]: _modal_total)
+        if training and with_grad and self._head_part is not None and not self._staged:
+            # (a stage: its weight-gradient call adds no slots; the heads add with atomics)
             for i, h in enumerate(heads):
                 h["g_part"] = self._head_part[i]
             self._wgrad_heads = heads                     # _backward's weight-gradient launch adds the slots to g_w / g_b
@@ -1525,6 +1647,7 @@ class _TwoTowerEngine(_FlatEngine):
             return                                         # heads + losses ride in the fusion tower's backward launch (_backward)
         self._loss_heads(heads, labels, not training)      # a training step's _prologue already cleared the losses
         self._stage_two_total(training)
+        self._modal_total(training)
 
     def _backward(self, xa, xb, fused_update: bool = False):
         """Backward of the whole model.  fused_update: also apply Adam + re-pack (single-GPU path; with a gradient
@@ -1544,20 +1667,25 @@ class _TwoTowerEngine(_FlatEngine):
             return
         a, b = self.MODS
         so = 1 if self._pending_bump else 0                 # (the forward of this step left the dropout counter un-advanced)
-        if self._fused_heads:
+        modal = self._modal
+        if modal:
+            pass                                            # the modalities-only stage: nothing of the fusion tower runs
+        elif self._fused_heads:
             # the three heads + multi-head CE in the prologue of this launch (m2m_tower_backward_heads): one launch less
             self.t_fus.backward_heads(B, self._heads, 2, self._labels, self.K, (self.logits, self.losses, self.preds),
                                       self.d_fused, fs, self.seed, so, sd)
         else:
             self.t_fus.backward(B, None, 0, self.dpool_fus, self.d_fused, fs, self.seed, so, sd)
-        if self.concat:
+        if modal:
+            d_a_part, d_b_part, sa_, sb_ = None, None, 0, 0   # the towers' backward starts from their heads' d_pooled alone
+        elif self.concat:
             d_a_part, d_b_part, sa_, sb_ = self.d_fused, self.d_fused.view(-1)[self.Na * D:], fs, fs
         else:
             self._fusion_backward()
             d_a_part, d_b_part, sa_, sb_ = self.d_out_a, self.d_out_b, self.Na * D, self.Nb * D
         main, s_a, s_f = self._streams()
-        wg_towers = [self.t_fus, self.t_a, self.t_b]
-        if self._early_fus_wgrad:
+        wg_towers = [self.t_a, self.t_b] if modal else [self.t_fus, self.t_a, self.t_b]
+        if self._early_fus_wgrad and not modal:
             s_f.wait_stream(main)
             with torch.cuda.stream(s_f):
                 self.t_fus.wgrad(B, self.seed, so, sd)
@@ -1594,7 +1722,7 @@ class _TwoTowerEngine(_FlatEngine):
             towers_wgrad(wg_towers, B, seed=self.seed, step=so, step_dev=sd, heads=self._wgrad_heads, K=self.K)
             main.wait_stream(s_e)
         self._pending_bump = False
-        if self._early_fus_wgrad:
+        if self._early_fus_wgrad and not modal:
             main.wait_stream(s_f)
         if fused_update:
             self._update(1.0)
@@ -1604,6 +1732,27 @@ class _TwoTowerEngine(_FlatEngine):
         the slot in hand, the embeddings' kept ranges) re-derived for the single-tower call of stage two."""
         self.t_fus.set_wgrad_overwrite(False)
         self._setup_wgrad([[self.t_fus]])
+
+    def _modal_stage_options(self):
+        """The same re-derivation for the modalities-only stage's weight-gradient launch: the two modality towers and their
+        embeddings, without the fusion tower (whose slot and kept ranges leave the table).  The embeddings keep their
+        single-owner ("=") form and their uncleared ranges where the table still has room; else they go back to adding."""
+        for t in (self.t_a, self.t_b, self.t_fus):
+            t.set_wgrad_overwrite(False)
+        self._setup_wgrad([[self.t_a, self.t_b]])
+        a, b = self.MODS
+        owned = [(e, self.grads[pre + "to_patch_embedding.0.weight"]) for e, pre in ((self.e_a, f"{a}_mixer."), (self.e_b, f"{b}_mixer."))
+                 if e.desc.wgrad_flags & L.WGRAD_OVERWRITE]
+        if owned and len(self._ranges_add) + len(owned) > L.MAX_GRAD_RANGES:
+            for e, _ in owned:
+                e.set_wgrad_overwrite(False)
+            owned = []
+        for _, gw in owned:
+            self._ranges_add.append(((gw.data_ptr() - self.flat_g.data_ptr()) // 4, gw.numel(), None, 1))
+        self._ranges_add.sort(key=lambda r: r[0])
+
+    def _modal_stage_packs(self) -> list:
+        return [self.t_a, self.e_a, self.t_b, self.e_b]
 
     def _update_chunks(self):
         """One chunk per parameter segment, in flat order: modality a (its patch embedding + tower), modality b, fusion tower
@@ -1854,7 +2003,7 @@ class MimicEngine(_FlatEngine):
         if prologue and side is main:
             # one stream: the step prologue rides in the input projection's launch, which then goes first (it reads none of the
             # counters; the static MLP draws its dropout masks from the bumped one)
-            head = (self.adam_state, self.drop_step, self.losses)
+            head = (self._head_adam(), self.drop_step, self.losses)
             self.e_time.forward(time, B, self.x0_time, step_head=head)
         elif prologue:
             self._prologue()
@@ -1869,7 +2018,9 @@ class MimicEngine(_FlatEngine):
         if ride:
             self.mlp.ride_flush()                           # (a launch of its own if no token launch took it)
         main.wait_stream(side)
-        self.t_fus.forward(self.fused, fs, B, self.fus_out, fs, None if hp else self.pool_fus, training, self.seed, 0, sd)
+        modal = training and self._modal                    # the modalities-only stage: no fusion tower
+        if not modal:
+            self.t_fus.forward(self.fused, fs, B, self.fus_out, fs, None if hp else self.pool_fus, training, self.seed, 0, sd)
         hw = self.head_weights
         heads = [self._head("static", self.pool_static, self.dpool_static, hw["static"], with_grad),
                  self._head("time", self.pool_time, self.dpool_time, hw["time"], with_grad),
@@ -1877,14 +2028,27 @@ class MimicEngine(_FlatEngine):
         if hp:
             heads[1]["tokens"] = (time_part.data_ptr(), self.Nt, fs)
             heads[2]["tokens"] = (self.fus_out, self.Nf, fs)
+        if modal:
+            heads = heads[:2]                               # (their total lands in losses[2]: _modal_total)
         heads_ce(heads, labels, B, D, self.K, out=(self.logits, self.losses, self.preds), zero_losses=not training,
                  weights=self._pass_weights(training))
         self._stage_two_total(training)
+        self._modal_total(training)
 
     def _backward(self, static, time, fused_update: bool = False):
         B, D = self.B, self.D
         fs = self.Nf * D
         sd = self.drop_step
+        if self._modal:
+            # the modalities-only stage: the static MLP's and the time tower's backward from their heads' d_pooled alone (d_out
+            # NULL), the time tower's and the projection's weight gradients as single calls -- on the main stream at any batch size
+            self.mlp.backward(static, B, None, 0, self.dpool_static)
+            self.t_time.backward(B, None, 0, self.dpool_time, self.dx0_time, self.Nt * D, self.seed, 0, sd)
+            self.t_time.wgrad(B, self.seed, 0, sd)
+            self.e_time.wgrad(time, self.dx0_time, B)
+            if fused_update:
+                self._update(1.0)
+            return
         self.t_fus.backward(B, None, 0, self.dpool_fus, self.d_fused, fs, self.seed, 0, sd)
         if self._frozen:
             # stage two: the time tower's backward, the static MLP's (riding or not) and the projection's weight gradient are
@@ -1931,6 +2095,9 @@ class MimicEngine(_FlatEngine):
             self.e_time.pack(force=True)
         main.wait_stream(s_b)
         main.wait_stream(s_f)
+
+    def _modal_stage_packs(self) -> list:
+        return [self.t_time, self.e_time]                   # (the static MLP reads the fp32 masters: no packed copies)
 
     @torch.no_grad()
     def evaluate(self, static, time, labels, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None):

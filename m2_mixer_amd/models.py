@@ -14,7 +14,9 @@ modules/train_test_module.py:72-150) are here; after `bind_engine(batch_size)` t
 (engine.py) over the module's OWN parameters -- `parameters()`, `state_dict()` and checkpoints see the live weights.
 `to_engine()` is the lower-level alternative: an engine over a copy of the weights, driven by a loop of its own.
 The towers are `m2_mixer_amd.modules` (HIP kernels under torch autograd); heads and losses are the same few torch ops the
-reference uses.  SoftAdapt / GradBlend weighting are outside the scope of this build and refused loudly.
+reference uses.  Gradient-Blending (`gradblend: True`, models/avmnist.py:211-234) is accepted by the AV-MNIST and MIMIC modules:
+`gb_weights` replaces the loss coefficients, and a bound module refreshes them on its engine (on_train_epoch_start, gradblend.py).
+SoftAdapt weighting is outside the scope of this build and refused loudly.
 """
 from __future__ import annotations
 
@@ -154,9 +156,16 @@ class _MultiLossModule(nn.Module):
         self.model_cfg = _Cfg(model_cfg if isinstance(model_cfg, dict) else dict(model_cfg))
         self.optimizer_cfg = dict(optimizer_cfg)
         self.scheduler_patience = self.optimizer_cfg.pop("scheduler_patience", 5)       # models/avmnist.py:171
-        for key in ("use_softadapt", "use_gradblend"):
-            if self.model_cfg.get(key, False):
-                raise NotImplementedError(f"{key}: loss re-weighting schemes are outside this build's scope")
+        if self.model_cfg.get("use_softadapt", False):
+            raise NotImplementedError("use_softadapt: loss re-weighting schemes are outside this build's scope")
+        # Gradient-Blending (models/avmnist.py:211-217, models/mimic.py:68-74): the reference reads `gradblend`; `use_gradblend`
+        # is accepted as an alias.  gb_epochs (extension): the retraining epochs of a refresh (gradblend.py:27: 20)
+        self.use_gradblend = bool(self.model_cfg.get("gradblend", False) or self.model_cfg.get("use_gradblend", False))
+        if self.use_gradblend and self.GB_ORDER is None:
+            raise NotImplementedError(f"gradblend: the reference has no Gradient-Blending for {type(self).__name__}")
+        self.gb_update_freq = int(self.model_cfg.get("gb_update_freq", 20))
+        self.gb_epochs = int(self.model_cfg.get("gb_epochs", 20))
+        self.gb_weights = None                       # [w, w, w] in the reference's list order (GB_ORDER) once computed
         self.mute = self.model_cfg.get("mute", None)
         self.freeze_modalities_on_epoch = self.model_cfg.get("freeze_modalities_on_epoch", None)
         self.random_modality_muting_on_freeze = self.model_cfg.get("random_modality_muting_on_freeze", False)
@@ -171,6 +180,36 @@ class _MultiLossModule(nn.Module):
         self._engine = None                          # bind_engine: the fused engine whose buffers hold this module's parameters
         self._two_stage = False                      # bind_engine(..., two_stage=True): the bound engine follows the freeze epoch
         self._engine_optimizer: Optional[EngineOptimizer] = None     # the latest configure_optimizers() of a bound module
+
+    #: the heads in the order of the reference's `gb_weights` list (None: the task has no Gradient-Blending)
+    GB_ORDER: Optional[Tuple[str, str, str]] = None
+
+    def _gb_loss(self, losses: Dict[str, torch.Tensor]):
+        """The Gradient-Blending total (models/avmnist.py:283-288, models/mimic.py:116-124) of {head name: loss}, in every mode;
+        None while there are no weights."""
+        if not self.use_gradblend or self.gb_weights is None:
+            return None
+        w = dict(zip(self.GB_ORDER, self.gb_weights))
+        a, b = self.MODS
+        return w["fusion"] * losses["fusion"] + w[a] * losses[a] + w[b] * losses[b]
+
+    def on_train_epoch_start(self, data=None, split: str = "train"):
+        """models/avmnist.py:219-234: every `gb_update_freq` epochs recompute the Gradient-Blending weights.  A bound module
+        runs gradblend.GradBlend on its engine over `data` (the resident training split: data.ResidentTensors /
+        ResidentAVMnist; val = its first 10 %) and writes the weights into the engine's loss-weight table (set_loss_weights: the
+        captured graph is kept and follows).  Returns the new {head: weight}, or None when nothing was due."""
+        if not self.use_gradblend or self.current_epoch % self.gb_update_freq != 0:
+            return None
+        if self._engine is None:
+            raise RuntimeError("on_train_epoch_start: Gradient-Blending runs on the fused engine: bind_engine(batch_size) first "
+                               "(an unbound module takes gb_weights as given)")
+        if data is None:
+            raise ValueError("on_train_epoch_start: gradblend needs the resident training split (data=)")
+        from .gradblend import GradBlend
+        w = GradBlend(self._engine, data, split=split, epochs=self.gb_epochs, seed=self.current_epoch).get_weights()
+        self.gb_weights = [w[h] for h in self.GB_ORDER]
+        self._engine.set_loss_weights(*(w[h] for h in self._engine.HEAD_NAMES))
+        return w
 
     # ---- pieces shared by the three tasks ----------------------------------------------------------------
     def _fusion_and_heads(self, n_a: int, n_b: int, dim_a: int, dim_b: int):
@@ -548,7 +587,9 @@ class _MultiLossModule(nn.Module):
         new = min(1, self.fusion_loss_weight + self.fusion_loss_change)
         if new == self.fusion_loss_weight:
             return scores
-        if self._engine is not None and self.ENGINE_LOSS_SCHEDULE:
+        if self._engine is not None and self.ENGINE_LOSS_SCHEDULE and self.gb_weights is None:
+            # (with Gradient-Blending weights in place the reference's loss no longer reads fusion_loss_weight: only the
+            # attribute moves)
             self._engine.set_fusion_loss_weight(float(new))
         self.fusion_loss_weight = new
         return scores
@@ -558,6 +599,7 @@ class AVMnistMixerMultiLoss(_MultiLossModule):
     """batch = {'image': (B,1,28,28), 'audio': (B,1,112,112), 'label': (B,)}"""
 
     MODS = ("image", "audio")
+    GB_ORDER = ("audio", "image", "fusion")         # on_train_epoch_start hands the encoders over as [audio, image] (models/avmnist.py:221)
 
     TEST_PRED_KEYS = ("preds", "preds_image", "preds_audio", "labels", "image_logits", "audio_logits", "logits")
 
@@ -588,6 +630,9 @@ class AVMnistMixerMultiLoss(_MultiLossModule):
         loss_fusion = self.fusion_criterion(logits, labels)
         ow = (1 - self.fusion_loss_weight) / 2
         loss = (self.fusion_loss_weight * loss_fusion + ow * loss_image + ow * loss_audio) * 3     # models/avmnist.py:289-290
+        gb = self._gb_loss({"image": loss_image, "audio": loss_audio, "fusion": loss_fusion})
+        if gb is not None:
+            loss = gb                                                                              # models/avmnist.py:283-288 (no x3)
         if self.modalities_freezed and mode == "train":
             loss = loss_fusion
         return {"preds": logits.argmax(dim=1), "preds_image": image_logits.argmax(dim=1),
@@ -636,6 +681,7 @@ class AVMnistMixerMultiLossUQ(AVMnistMixerMultiLoss):
     does not reach the engine."""
 
     ENGINE_LOSS_SCHEDULE = False
+    GB_ORDER = None                                  # (models/avmnist.py:447-572 has no Gradient-Blending)
 
     def __init__(self, model_cfg, optimizer_cfg, **kwargs):
         super().__init__(model_cfg, optimizer_cfg, **kwargs)
@@ -776,6 +822,7 @@ class MimicMixerMultiLoss(_MultiLossModule):
     """batch = (static (B,5), time (B,24,12), labels (B,))"""
 
     MODS = ("static", "time")
+    GB_ORDER = ("static", "time", "fusion")         # models/mimic.py:116-124
 
     def __init__(self, model_cfg, optimizer_cfg, **kwargs):
         super().__init__(model_cfg, optimizer_cfg, **kwargs)
@@ -798,6 +845,9 @@ class MimicMixerMultiLoss(_MultiLossModule):
         loss_time = self.criterion(logits_time, labels)
         ow = (1 - self.fusion_loss_weight) / 2
         loss = self.fusion_loss_weight * loss_fusion + ow * loss_static + ow * loss_time          # models/mimic.py:115-121 (no x3)
+        gb = self._gb_loss({"static": loss_static, "time": loss_time, "fusion": loss_fusion})
+        if gb is not None:
+            loss = gb                                                                             # models/mimic.py:116-124
         return {"preds": torch.softmax(logits, dim=1), "preds_static": torch.softmax(logits_static, dim=1),
                 "preds_time": torch.softmax(logits_time, dim=1), "labels": labels.long(), "loss": loss,
                 "loss_fusion": loss_fusion, "loss_static": loss_static, "loss_time": loss_time, "logits": logits,
