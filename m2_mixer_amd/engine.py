@@ -27,12 +27,16 @@ What changes relative to the module path (modules/mixer.py + torch autograd):
     a schedule on the device (csrc/feed.hip: m2m_feed_gather_muted);
   * train_modalities_only(): the mirror image -- the loss is loss_a + loss_b, no fusion function or fusion tower runs, the fusion
     keys are never written (the unimodal models of Gradient-Blending); clone() and probe() are the other two pieces
-    gradblend.GradBlend is built from.
+    gradblend.GradBlend is built from.  Either stage is one Stage record held by the engine family and
+    one pair of hooks per engine class (_stage_options, _stage_packs).
+This file is the engines: the step, the stages, the optimizer, capture.  The device-side accumulators (ScoreTable, RankBuffer,
+EpochFeed) live in accumulators.py, the parameter-layout functions in layout.py; every name stays importable from here.
 """
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Dict, List, Optional, Sequence, Tuple
+from contextlib import contextmanager
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import ctypes as C
 import weakref
@@ -41,10 +45,30 @@ import torch
 
 from . import _lib as L
 from . import config
-from .runtime import (AdamPackPlan, BLOCK_FIELDS, BLOCK_KEYS, EmbedRuntime, MlpRuntime, TowerRuntime, block_param_shapes, heads_bce,
+# this module stays the import surface: the accumulators and the layout functions are re-exported under their old names
+from .accumulators import EpochFeed, RankBuffer, ScoreTable  # noqa: F401
+from .layout import (ENGINE_FUSIONS, _head_shapes, _is_layer_norm, _num_patch, _tower_shapes,  # noqa: F401
+                     avmnist_param_shapes, frozen_key_prefixes, fusion_function_name, fusion_tokens, mimic_param_shapes,
+                     trainable_flat_ranges, two_tower_param_shapes)
+from .runtime import (AdamPackPlan, BLOCK_FIELDS, BLOCK_KEYS, EmbedRuntime, MlpRuntime, TowerRuntime, heads_bce,
                       heads_ce, heads_edl, can_group, can_group_embeds, can_pack_all, embeds_forward, pack_all,
                       towers_backward, towers_forward, towers_forward_embeds_ok, towers_wgrad, wgrad_slot_groups,
                       _embed_ptrs, _grad_ranges, _tower_ptrs)
+
+_ELEM_FUSION_MODE = {"SumFusion": L.FUSION_SUM, "MeanFusion": L.FUSION_MEAN, "MaxFusion": L.FUSION_MAX}
+
+
+class Stage(NamedTuple):
+    """A training stage of an engine family: what it trains and under which loss.  Stage one (everything, `loss_weights`) is
+    the absence of one."""
+    name: str                                    # what `_frozen` / `_modal` test
+    title: str                                   # the stage in the words of its messages
+    weights: Tuple[float, float, float]          # the training coefficients of the heads (HEAD_NAMES order)
+    invert: bool                                 # which side of frozen_key_prefixes trains (trainable_flat_ranges' `invert`)
+
+
+FROZEN = Stage("frozen", "stage two (freeze_modalities)", (0.0, 0.0, 1.0), False)
+MODAL = Stage("modal", "the modalities-only stage (train_modalities_only)", (1.0, 1.0, 0.0), True)
 
 
 def config_fused_update(n_params: int = 0) -> bool:
@@ -60,131 +84,6 @@ def config_fused_update(n_params: int = 0) -> bool:
     return n_params > 0
 
 
-def _num_patch(c: dict) -> int:
-    return (c["image_size"][0] // c["patch_size"]) * (c["image_size"][1] // c["patch_size"])
-
-
-def _tower_shapes(s: "OrderedDict[str, tuple]", prefix: str, c: dict, N: int, embed: Optional[str]):
-    D = c["hidden_dim"]
-    if embed == "patch":
-        s[prefix + "to_patch_embedding.0.weight"] = (D, c["in_channels"], c["patch_size"], c["patch_size"])
-        s[prefix + "to_patch_embedding.0.bias"] = (D,)
-    elif embed == "proj":
-        s[prefix + "proj.weight"] = (c["proj_dim"], c["embedding_dim"])
-        s[prefix + "proj.bias"] = (c["proj_dim"],)
-    shapes = block_param_shapes(D, N, c["token_dim"], c["channel_dim"])
-    for i in range(c["num_mixers"]):
-        for f in BLOCK_FIELDS:
-            s[f"{prefix}mixer_blocks.{i}.{BLOCK_KEYS[f]}"] = shapes[f]
-    s[prefix + "layer_norm.weight"] = (D,)
-    s[prefix + "layer_norm.bias"] = (D,)
-
-
-def _head_shapes(s, names: Sequence[str], dims: Sequence[int], K: int):
-    for n, d in zip(names, dims):
-        key = "classifier_fusion.classifer." if n == "fusion" else f"classifier_{n}."     # sic: classification.py:87
-        s[key + "weight"] = (K, d)
-        s[key + "bias"] = (K,)
-
-
-#: fusion functions (cfg["multimodal"]["fusion_function"]) the two-tower engines build; ConcatFusion when the key is absent
-ENGINE_FUSIONS = ("ConcatFusion", "SumFusion", "MeanFusion", "MaxFusion", "BiModalGatedUnit")
-_ELEM_FUSION_MODE = {"SumFusion": L.FUSION_SUM, "MeanFusion": L.FUSION_MEAN, "MaxFusion": L.FUSION_MAX}
-
-
-def fusion_function_name(mm: dict) -> str:
-    """cfg["multimodal"]'s fusion function; refuses the ones the engines do not build (ConcatDynaFusion, ExtraConcatFusion)."""
-    name = mm.get("fusion_function", "ConcatFusion")
-    if name not in ENGINE_FUSIONS:
-        raise RuntimeError(f"multimodal.fusion_function = {name!r}: the fused engines build {', '.join(ENGINE_FUSIONS)}")
-    return name
-
-
-def fusion_tokens(mm: dict, na: int, nb: int) -> int:
-    """Tokens of the fusion tower: the registry's own get_output_shape(na, nb, dim=1) (models/avmnist.py:183-186), so unequal
-    token counts are refused as the reference refuses them (sum / mean / max: ValueError)."""
-    from .modules import fusion as F
-    name = fusion_function_name(mm)
-    if name == "BiModalGatedUnit":
-        if na != nb:       # (its get_output_shape does not check; the reference fails inside torch.cat)
-            raise RuntimeError(f"multimodal.fusion_function = BiModalGatedUnit needs equal token counts, got {na} and {nb}")
-        return na
-    fn = F.ConcatFusion(dim=1) if name == "ConcatFusion" else getattr(F, name)()
-    return int(fn.get_output_shape(na, nb, dim=1))
-
-
-def two_tower_param_shapes(cfg: dict, mods: Tuple[str, str]) -> "OrderedDict[str, tuple]":
-    """state-dict key -> shape in the reference's creation order (models/avmnist.py:181-191, models/mmimdb.py:35-45): the two
-    towers, the fusion function's parameters (BiModalGatedUnit only), the fusion mixer, the three heads."""
-    s: "OrderedDict[str, tuple]" = OrderedDict()
-    a, b = mods
-    mm = cfg["multimodal"]
-    na, nb = _num_patch(cfg[a]), _num_patch(cfg[b])
-    nf = fusion_tokens(mm, na, nb)
-    _tower_shapes(s, f"{a}_mixer.", cfg[a], na, "patch")
-    _tower_shapes(s, f"{b}_mixer.", cfg[b], nb, "patch")
-    if fusion_function_name(mm) == "BiModalGatedUnit":
-        i1, i2, o = mm["mod1_in"], mm["mod2_in"], mm["out_size"]
-        for k, fan_in in (("mod1_hidden", i1), ("mod2_hidden", i2), ("z_hidden", i1 + i2)):       # modules/fusion.py:10-14
-            s[f"fusion_function.{k}.weight"] = (o, fan_in)
-            s[f"fusion_function.{k}.bias"] = (o,)
-    _tower_shapes(s, "fusion_mixer.", mm, nf, None)
-    _head_shapes(s, (a, b, "fusion"), (cfg[a]["hidden_dim"], cfg[b]["hidden_dim"], cfg["multimodal"]["hidden_dim"]),
-                 cfg["num_classes"])
-    return s
-
-
-def avmnist_param_shapes(cfg: dict) -> "OrderedDict[str, tuple]":
-    return two_tower_param_shapes(cfg, ("image", "audio"))
-
-
-def mimic_param_shapes(cfg: dict) -> "OrderedDict[str, tuple]":
-    """Creation order of models/mimic.py:39-49: time_mixer, static_extractor, fusion_mixer, three classifiers."""
-    s: "OrderedDict[str, tuple]" = OrderedDict()
-    t, st = cfg["time"], cfg["static"]
-    _tower_shapes(s, "time_mixer.", t, t["num_patch"], "proj")
-    for i in range(st["num_blocks"]):
-        s[f"static_extractor.module_list.{3 * i}.weight"] = (st["hidden_dim"], st["input_dim"] if i == 0 else st["hidden_dim"])
-        s[f"static_extractor.module_list.{3 * i}.bias"] = (st["hidden_dim"],)
-    k = 3 * st["num_blocks"]
-    s[f"static_extractor.module_list.{k}.weight"] = (st["output_dim"], st["hidden_dim"])
-    s[f"static_extractor.module_list.{k}.bias"] = (st["output_dim"],)
-    _tower_shapes(s, "fusion_mixer.", cfg["multimodal"], 1 + t["num_patch"], None)
-    _head_shapes(s, ("static", "time", "fusion"), (st["output_dim"], t["hidden_dim"], cfg["multimodal"]["hidden_dim"]),
-                 cfg["num_classes"])
-    return s
-
-
-def trainable_flat_ranges(shapes: "Dict[str, tuple]", frozen_prefixes: Sequence[str], invert: bool = False) -> List[Tuple[int, int]]:
-    """Stage two of the reference's two-stage training (models/avmnist.py:314-324): the contiguous flat ranges [lo, hi) of the
-    parameters that keep training, given the ordered state-dict shapes and the key prefixes that freeze.  Neighbouring trainable
-    parameters are merged; the ranges are sorted and disjoint, and with the frozen keys' ranges they tile [0, n_params).  Pure:
-    no device, no library.
-    invert=True: the complement -- the ranges of the keys that DO start with one of the prefixes (the modalities-only stage
-    trains exactly what stage two freezes: train_modalities_only)."""
-    frozen = tuple(frozen_prefixes)
-    out: List[Tuple[int, int]] = []
-    off = 0
-    for k, shp in shapes.items():
-        cnt = 1
-        for d in shp:
-            cnt *= int(d)
-        if k.startswith(frozen) == invert:
-            if out and out[-1][1] == off:
-                out[-1] = (out[-1][0], off + cnt)
-            else:
-                out.append((off, off + cnt))
-        off += cnt
-    return out
-
-
-def frozen_key_prefixes(names: Sequence[str]) -> Tuple[str, ...]:
-    """Key prefixes that stage two freezes for the modalities `names` (_MultiLossModule._freeze_modalities): the two modality
-    towers with their embeddings (MIMIC: static_extractor, time_mixer) and their two heads."""
-    towers = ("static_extractor.", "time_mixer.") if tuple(names) == ("static", "time") else tuple(f"{n}_mixer." for n in names)
-    return towers + tuple(f"classifier_{n}." for n in names)
-
-
 def _exchange_mode(grad_sync) -> str:
     """How a step exchanges gradients: "none" (grad_sync None: single GPU), "pipelined" (an object with a true `pipelined`:
     parallel.PipelinedGradSync) or "single" (any other callable(flat_grad) -> scale)."""
@@ -193,299 +92,10 @@ def _exchange_mode(grad_sync) -> str:
     return "pipelined" if getattr(grad_sync, "pipelined", False) else "single"
 
 
-def _is_layer_norm(k: str) -> bool:
-    return ("layer_norm." in k) or k.endswith("token_mix.0.weight") or k.endswith("token_mix.0.bias") \
-        or k.endswith("channel_mix.0.weight") or k.endswith("channel_mix.0.bias")
-
-
-class ScoreTable:
-    """The count table of one split (train / val / test) in device memory: every step ADDS its batch's counts (csrc/scores.hip,
-    one launch, capturable), the host reads it once per epoch and derives the reference's scores in float64 (scores.py).
-    kind "multiclass": per head a (K, K) confusion matrix [label][pred] + one cell of skipped rows (label or prediction outside
-    [0, K)); "multilabel": per head (K, 4) = tp, fp, fn, tn per label."""
-
-    def __init__(self, task: str, head_names: Sequence[str], K: int, device):
-        from . import scores as S
-        self.task, self.kind, self.head_names, self.K = task, S.TASK_KIND[task], tuple(head_names), int(K)
-        lim = L.SCORES_MAX_LABELS if self.kind == "multilabel" else L.SCORES_MAX_CLASSES
-        if not 1 <= self.K <= lim:
-            raise RuntimeError(f"ScoreTable: {self.kind} K = {K}: the scores kernel takes 1..{lim}")
-        self.cells = self.K * 4 if self.kind == "multilabel" else self.K * self.K + 1
-        self.table = torch.zeros(len(self.head_names), self.cells, dtype=torch.int64, device=device)
-        self.skipped = None                          # multiclass: per-head skipped rows as of the last counts()
-
-    def add(self, preds: torch.Tensor, truth: torch.Tensor):
-        """Enqueue the launch that adds one batch: preds int32 (nheads, B) / (nheads, B, K), truth int64 labels (B) / float
-        targets (B, K).  Nothing synchronises."""
-        nh, B = len(self.head_names), int(preds.shape[1])
-        ml = self.kind == "multilabel"
-        want_p, want_t = ((nh, B, self.K), (B, self.K)) if ml else ((nh, B), (B,))
-        if (tuple(preds.shape) != want_p or tuple(truth.shape) != want_t or preds.dtype != torch.int32
-                or truth.dtype != (torch.float32 if ml else torch.int64) or not preds.is_contiguous() or not truth.is_contiguous()
-                or preds.device != self.table.device or truth.device != self.table.device):
-            raise RuntimeError(f"ScoreTable.add: {self.kind} needs contiguous device tensors preds int32 {want_p} and "
-                               f"{'targets float32' if ml else 'labels int64'} {want_t}")
-        fn = L.lib().m2m_scores_multilabel if ml else L.lib().m2m_scores_multiclass
-        L.check(fn(preds.data_ptr(), truth.data_ptr(), nh, B, self.K, self.table.data_ptr(), L.stream_ptr()), "scores_" + self.kind)
-
-    def reset(self):
-        """Clear the table: an asynchronous fill on the current stream, in place -- captured graphs keep adding into it."""
-        self.table.zero_()
-
-    def counts(self) -> torch.Tensor:
-        """The table on the host, int64: (nheads, K, K) or (nheads, K, 4).  One device-to-host copy: the only synchronisation."""
-        host = self.table.cpu()
-        if self.kind == "multilabel":
-            return host.view(-1, self.K, 4)
-        self.skipped = host[:, -1].clone()
-        return host[:, :-1].reshape(-1, self.K, self.K)
-
-    def compute(self) -> Dict[str, float]:
-        """The reference's score names of this task -> float (fusion head: plain names; other heads: `_<modality>` appended)."""
-        from . import scores as S
-        return S.task_scores(self.task, self.counts().numpy(), self.head_names)
-
-
-class RankBuffer:
-    """The ranking buffer of one split in device memory: every step APPENDS the fp32 softmax of its batch's logits and the
-    labels (csrc/rank.hip: m2m_rank_append, one launch, capturable; the row cursor lives in `state` on the device), the host
-    asks once per epoch for four integers per row (m2m_rank_counts) and derives average precision / ROC-AUC in float64
-    (scores.rank_scores).  probs (nheads, K, capacity): a class column is contiguous; labels (capacity) int32, -1 where the
-    label was outside [0, K); state: L.RANK_STATE_WORDS uint32 (held as int32) = rows appended (keeps counting past capacity),
-    arrival ticket, rows without a label, reserved."""
-
-    def __init__(self, task: str, head_names: Sequence[str], K: int, capacity: int, device):
-        from . import scores as S
-        if task not in S.RANK_SCORES:
-            raise RuntimeError(f"RankBuffer: no ranking scores for task {task!r} (built: {', '.join(S.RANK_SCORES)}; multilabel "
-                               "ranking is not)")
-        self.task, self.head_names, self.K, self.capacity = task, tuple(head_names), int(K), int(capacity)
-        if not 1 <= self.K <= L.SCORES_MAX_CLASSES:
-            raise RuntimeError(f"RankBuffer: K = {K}: the ranking kernels take 1..{L.SCORES_MAX_CLASSES}")
-        if self.capacity < 1:
-            raise RuntimeError(f"RankBuffer: capacity = {capacity}: at least one row")
-        self.probs = torch.zeros(len(self.head_names), self.K, self.capacity, device=device)
-        self.labels = torch.full((self.capacity,), -1, dtype=torch.int32, device=device)
-        self.state = torch.zeros(L.RANK_STATE_WORDS, dtype=torch.int32, device=device)
-        self.skipped = None                          # rows without a label as of the last counts()
-
-    def add(self, logits: torch.Tensor, labels: torch.Tensor):
-        """Enqueue the launch that appends one batch: logits float32 (nheads, B, K), labels int64 (B).  Nothing synchronises."""
-        nh, B = len(self.head_names), int(logits.shape[1]) if logits.dim() == 3 else -1
-        want_x, want_l = (nh, B, self.K), (B,)
-        if (tuple(logits.shape) != want_x or tuple(labels.shape) != want_l or logits.dtype != torch.float32
-                or labels.dtype != torch.int64 or not logits.is_contiguous() or not labels.is_contiguous()
-                or logits.device != self.state.device or labels.device != self.state.device):
-            raise RuntimeError(f"RankBuffer.add: needs contiguous device tensors logits float32 ({nh}, B, {self.K}) and labels "
-                               f"int64 (B), got {tuple(logits.shape)} {logits.dtype} and {tuple(labels.shape)} {labels.dtype}")
-        L.check(L.lib().m2m_rank_append(logits.data_ptr(), labels.data_ptr(), nh, B, self.K, self.probs.data_ptr(),
-                                        self.labels.data_ptr(), self.capacity, self.state.data_ptr(), L.stream_ptr()), "rank_append")
-
-    def reset(self):
-        """Empty the buffer: an asynchronous fill of `state` on the current stream, in place -- captured graphs keep appending
-        into the same memory (the rows behind the cursor are dead)."""
-        self.state.zero_()
-
-    def rows(self) -> int:
-        """Rows appended since the last reset (one device-to-host copy; may exceed `capacity`: see counts)."""
-        return int(self.state[0].item()) & 0xFFFFFFFF
-
-    def counts(self) -> Tuple[torch.Tensor, torch.Tensor]:
-        """(counts (nheads, n, 4) int64 = n_ge, p_ge, n_gt, p_gt per row, labels (n) int64) on the host.  Reads `state`, launches
-        m2m_rank_counts over the n rows, copies back: the only synchronisation."""
-        st = self.state.cpu().numpy().view("uint32")
-        n = int(st[0])
-        if n > self.capacity:
-            raise RuntimeError(f"RankBuffer: overflow: capacity {self.capacity} rows, {n} rows seen since the last reset "
-                               "(rank_capacity= sets the capacity)")
-        self.skipped = int(st[2])
-        nh = len(self.head_names)
-        out = torch.zeros(nh, n, 4, dtype=torch.int32, device=self.state.device)
-        if n:
-            L.check(L.lib().m2m_rank_counts(self.probs.data_ptr(), self.labels.data_ptr(), nh, n, self.K, self.capacity,
-                                            out.data_ptr(), L.stream_ptr()), "rank_counts")
-        return out.cpu().to(torch.int64), self.labels[:n].cpu().to(torch.int64)
-
-    def compute(self, names: Optional[Sequence[str]] = None) -> Dict[str, float]:
-        """The task's ranking score names (scores.RANK_SCORES; `names`: any of auroc / ap_macro / roc_auc_macro) -> float
-        (fusion head: plain names; other heads: `_<modality>` appended)."""
-        from . import scores as S
-        counts, labels = self.counts()
-        return S.task_rank_scores(self.task, counts.numpy(), labels.numpy(), self.K, self.head_names, names)
-
-
-class EpochFeed:
-    """One split's resident tensors behind a device-side permutation and cursor (csrc/feed.hip): a step
-    gathers its own batch (m2m_feed_gather: rows perm[(cursor + r) % n] of every source into the step's input slots, the cursor
-    advanced on the device) and adds its own losses and hit counts to the epoch's accumulators (m2m_epoch_accumulate) -- both
-    capturable, so a graph from engine.capture_feed replays without arguments and an epoch is read back once.
-
-    sources: the split's tensors in the engine's batch order (AV-MNIST: image, audio, labels), contiguous, on `device`, with the
-    dtypes the engine's inputs have; rows of a multiple of 4 bytes.  The feed owns
-      perm    (n) int32, the epoch's sample order
-      state   L.FEED_STATE_WORDS uint32 (held as int32): cursor, reserved (zero), n, wrapped rows
-      sums    (2 * nloss) float64: step losses | the same weighted by the step's batch size
-      counts  (nheads + 2) int64: hits per head | steps | samples
-    nloss / nheads follow the first engine the feed is used with (multilabel predictions have no hit count: nheads = 0).
-    Single GPU only: every rank of a data-parallel run would need its shard of the order (out of scope).
-
-    muting=True (stage two's random modality muting, models/avmnist.py:243-256): the feed also owns
-      mute_codes  (ceil(n / B)) int32, one code per step of the epoch: 0 mutes nothing, s + 1 mutes source s (start writes them)
-      mute_state  L.FEED_MUTE_STATE_WORDS uint32 (held as int32): the step index, steps that ran past the schedule
-    and gather_into uses m2m_feed_gather_muted: the muted source's slot is filled with zero bytes, its rows are not read.
-    Both are allocated once: a captured graph keeps their pointers.  Off (the default): neither exists, nothing new is launched."""
-
-    def __init__(self, sources: Sequence[torch.Tensor], batch_size: int, device, muting: bool = False):
-        self.device = torch.device(device)
-        self.sources = tuple(sources)
-        self.B = int(batch_size)
-        if not 1 <= len(self.sources) <= L.FEED_MAX_SOURCES:
-            raise ValueError(f"EpochFeed: 1..{L.FEED_MAX_SOURCES} sources, got {len(self.sources)}")
-        if self.B < 1:
-            raise ValueError("EpochFeed: batch_size >= 1")
-        self.n = int(self.sources[0].shape[0])
-        if not 1 <= self.n < 2 ** 31:
-            raise ValueError(f"EpochFeed: the split needs 1 <= n < 2^31 rows, got {self.n}")
-        for i, t in enumerate(self.sources):
-            if t.device != self.device or not t.is_contiguous() or t.dim() < 1 or int(t.shape[0]) != self.n:
-                raise ValueError(f"EpochFeed: source {i} must be a contiguous tensor of {self.n} rows on {self.device}")
-            if self._row_bytes(t) < 4 or self._row_bytes(t) % 4:
-                raise ValueError(f"EpochFeed: source {i} has rows of {self._row_bytes(t)} bytes; the gather copies multiples of 4")
-        self.perm = torch.arange(self.n, dtype=torch.int32, device=self.device)
-        self._state0 = torch.tensor([0, 0, self.n, 0], dtype=torch.int32, device=self.device)
-        self.state = self._state0.clone()
-        self.mute_codes = self.mute_state = None
-        if muting:
-            self.mute_codes = torch.zeros((self.n + self.B - 1) // self.B, dtype=torch.int32, device=self.device)
-            self.mute_state = torch.zeros(L.FEED_MUTE_STATE_WORDS, dtype=torch.int32, device=self.device)
-        self._acc: Optional[torch.Tensor] = None         # sums and counts in one 8-byte-cell buffer: one copy reads both
-        self.nloss = self.nheads = None
-        self.sums = self.counts = None
-
-    @staticmethod
-    def _row_bytes(t: torch.Tensor) -> int:
-        return int(t[0].numel()) * t.element_size()
-
-    def bind(self, engine):
-        """Size the accumulators for `engine`'s losses and heads (first use), or check that they fit it."""
-        nloss = int(engine.losses.numel())
-        nheads = int(engine.preds.shape[0]) if engine.preds.dim() == 2 else 0
-        if self._acc is None:
-            self.nloss, self.nheads = nloss, nheads
-            self._acc = torch.zeros(2 * nloss + nheads + 2, dtype=torch.int64, device=self.device)
-            self.sums, self.counts = self._acc[:2 * nloss].view(torch.float64), self._acc[2 * nloss:]
-        elif (nloss, nheads) != (self.nloss, self.nheads):
-            raise RuntimeError(f"EpochFeed: accumulators sized for {self.nloss} losses / {self.nheads} heads, the engine has "
-                               f"{nloss} / {nheads}")
-
-    def new_slots(self, batch_size: Optional[int] = None) -> Tuple[torch.Tensor, ...]:
-        """Zeroed input slots of one step: the sources' row shapes and dtypes at `batch_size` rows (default: the feed's)."""
-        B = self.B if batch_size is None else int(batch_size)
-        return tuple(torch.zeros(B, *t.shape[1:], dtype=t.dtype, device=self.device) for t in self.sources)
-
-    def start(self, order=None, muting=None):
-        """Begin an epoch: write its sample order (a host or device index tensor of n values in [0, n); None: identity) IN PLACE
-        and zero the cursor, the wrapped count and the accumulators, all on the current stream -- captured graphs keep reading
-        the same memory.  A given order is checked against [0, n) first (the one synchronisation: an index outside the split
-        would read outside it).
-        muting (a feed built with muting=True): the epoch's codes, one per step, at most ceil(n / B), each in [0, nsrc - 1] -- the
-        last source, the labels, cannot be muted; written in place, the rest of the schedule zero; None: all zeros.  The step
-        index and the overflow word are reset."""
-        codes = None
-        if muting is not None:
-            if self.mute_codes is None:
-                raise ValueError("EpochFeed.start: a muting schedule needs a feed built with muting=True")
-            codes = torch.as_tensor(muting).detach().cpu()
-            cap, hi_code = int(self.mute_codes.numel()), len(self.sources) - 1
-            if codes.dim() != 1 or codes.dtype.is_floating_point or codes.dtype == torch.bool or int(codes.numel()) > cap:
-                raise ValueError(f"EpochFeed.start: the muting schedule must hold at most {cap} integer codes, got "
-                                 f"{tuple(codes.shape)} {codes.dtype}")
-            if codes.numel() and (int(codes.min()) < 0 or int(codes.max()) > hi_code):
-                raise ValueError(f"EpochFeed.start: muting codes span [{int(codes.min())}, {int(codes.max())}]; allowed are 0 (nothing) "
-                                 f"and 1..{hi_code} (source s + 1; the last source, the labels, cannot be muted)")
-        if order is None:
-            torch.arange(self.n, out=self.perm)
-        else:
-            order = torch.as_tensor(order)
-            if order.dim() != 1 or int(order.numel()) != self.n or order.dtype.is_floating_point or order.dtype == torch.bool:
-                raise ValueError(f"EpochFeed.start: the order must hold {self.n} integer indices, got {tuple(order.shape)} {order.dtype}")
-            lo, hi = (int(v) for v in torch.stack((order.min(), order.max())).cpu())
-            if lo < 0 or hi >= self.n:
-                raise ValueError(f"EpochFeed.start: the order's indices span [{lo}, {hi}], the split has rows [0, {self.n})")
-            self.perm.copy_(order.to(torch.int32))
-        self.state.copy_(self._state0)
-        if self.mute_codes is not None:
-            self.mute_codes.zero_()
-            if codes is not None and codes.numel():
-                self.mute_codes[:codes.numel()].copy_(codes.to(torch.int32))
-            self.mute_state.zero_()
-        if self._acc is not None:
-            self._acc.zero_()
-
-    def _state_host(self):
-        return self.state.cpu().numpy().view("uint32")
-
-    def rows(self) -> int:
-        """Rows handed out since start() (the cursor; one device-to-host copy)."""
-        return int(self._state_host()[0])
-
-    def check(self):
-        """Raise when a gather ran past the end of the epoch (its rows wrapped around to the order's head)."""
-        st = self._state_host()
-        if int(st[3]):
-            raise RuntimeError(f"EpochFeed: {int(st[0])} rows were fed from a split of {self.n}: {int(st[3])} row(s) wrapped around "
-                               "to the head of the order (a replay past the end of the epoch)")
-        if self.mute_state is not None:
-            ms = self.mute_state.cpu().numpy().view("uint32")
-            if int(ms[1]):
-                raise RuntimeError(f"EpochFeed: {int(ms[0])} gathers ran against a muting schedule of {int(self.mute_codes.numel())} "
-                                   f"steps: {int(ms[1])} step(s) past its end muted nothing")
-
-    def read(self):
-        """(sums float64 (2 * nloss), counts int64 (nheads + 2)) on the host as numpy: one copy, the epoch's only synchronisation."""
-        if self._acc is None:
-            raise RuntimeError("EpochFeed.read: no engine has used this feed yet")
-        host = self._acc.cpu().numpy()
-        return host[:2 * self.nloss].view("float64").copy(), host[2 * self.nloss:].copy()
-
-    def gather_into(self, slots: Sequence[torch.Tensor]):
-        """Enqueue the gather of the next slots[0].shape[0] rows of the order into `slots` (one per source, as new_slots makes
-        them; any batch size: the ragged tail's engine has its own).  Nothing synchronises."""
-        if len(slots) != len(self.sources):
-            raise ValueError(f"EpochFeed.gather_into: {len(self.sources)} slots (one per source), got {len(slots)}")
-        B = int(slots[0].shape[0])
-        desc = (L.FeedSrc * len(slots))()
-        for d, s, t in zip(desc, self.sources, slots):
-            if (t.dtype != s.dtype or tuple(t.shape) != (B, *s.shape[1:]) or not t.is_contiguous() or t.device != self.device):
-                raise ValueError(f"EpochFeed.gather_into: a slot must be a contiguous {s.dtype} tensor ({B}, {', '.join(map(str, s.shape[1:]))}) "
-                                 f"on {self.device}, got {t.dtype} {tuple(t.shape)}")
-            d.src, d.dst, d.row_bytes = s.data_ptr(), t.data_ptr(), self._row_bytes(s)
-        if self.mute_codes is not None:
-            L.check(L.lib().m2m_feed_gather_muted(desc, len(slots), self.perm.data_ptr(), B, self.state.data_ptr(),
-                                                  self.mute_codes.data_ptr(), int(self.mute_codes.numel()), self.mute_state.data_ptr(),
-                                                  L.stream_ptr()), "feed_gather_muted")
-            return
-        L.check(L.lib().m2m_feed_gather(desc, len(slots), self.perm.data_ptr(), B, self.state.data_ptr(), L.stream_ptr()), "feed_gather")
-
-    def accumulate(self, engine, labels: Optional[torch.Tensor]):
-        """Enqueue the launch that adds `engine`'s step (its losses, its preds against `labels`, its batch size) to the epoch's
-        accumulators.  Nothing synchronises."""
-        self.bind(engine)
-        preds = engine.preds if self.nheads else None
-        if self.nheads and (labels is None or labels.dtype != torch.int64 or tuple(labels.shape) != (engine.B,) or not labels.is_contiguous()
-                            or preds.dtype != torch.int32 or not preds.is_contiguous()):
-            raise RuntimeError(f"EpochFeed.accumulate: hit counts need contiguous labels int64 ({engine.B},) and preds int32")
-        L.check(L.lib().m2m_epoch_accumulate(engine.losses.data_ptr(), self.nloss, L.ptr(preds), L.ptr(labels) if self.nheads else 0,
-                                             self.nheads, engine.B, self.sums.data_ptr(), self.counts.data_ptr(), L.stream_ptr()),
-                "epoch_accumulate")
-
-
 class _FlatEngine:
     """Flat parameter / gradient / Adam buffers, the optimizer, data-parallel hooks and hipGraph capture.
     Subclasses supply `_param_shapes(cfg)`, `_segment_of(key)`, `_build()` (which names `_towers` and `_embeds`),
-    `_forward(...)`, `_backward(...)`."""
-
-    SEGMENTS: Tuple[str, ...] = ()
+    `_forward(...)`, `_backward(...)`, `_eval_outputs()` (evaluate's dict) and `_stage_packs()` (what a stage's update re-packs)."""
 
     #: the task whose score names a ScoreTable of this engine reports (scores.TASK_SCORES)
     SCORES_TASK: str = ""
@@ -515,10 +125,7 @@ class _FlatEngine:
                 raise RuntimeError("share=: the other engine must hold the same model on the same device")
             self.flat_p, self.flat_g, self.flat_m, self.flat_v = share.flat_p, share.flat_g, share.flat_m, share.flat_v
         else:
-            self.flat_p = torch.zeros(n, device=dev)
-            self.flat_g = torch.zeros(n, device=dev)
-            self.flat_m = torch.zeros(n, device=dev)
-            self.flat_v = torch.zeros(n, device=dev)
+            self.flat_p, self.flat_g, self.flat_m, self.flat_v = (torch.zeros(n, device=dev) for _ in range(4))
         self.params: Dict[str, torch.Tensor] = OrderedDict()
         self.grads: Dict[str, torch.Tensor] = OrderedDict()
         self.exp_avg: Dict[str, torch.Tensor] = OrderedDict()        # Adam's first / second moments, same keys
@@ -550,25 +157,20 @@ class _FlatEngine:
             # graph follows set_fusion_loss_weight / set_loss_weights without being captured again
             self.loss_weights = torch.tensor(self._head_weight_list(), dtype=torch.float32, device=dev)
             self._loss_weight_group = {"fused_heads": False}      # (shared by the siblings, like the table itself)
-            # the training stage of the engine family (freeze_modalities: "frozen", train_modalities_only: "modal"): shared by
-            # existing and later siblings
-            self._stage_group = {"frozen": False, "modal": False, "weights": None, "members": []}
+            # the training stage of the engine family (None: stage one; freeze_modalities: FROZEN, train_modalities_only: MODAL)
+            # with its device table of coefficients: shared by existing and later siblings
+            self._stage_group = {"stage": None, "weights": None, "members": []}
         self.seed = (share.seed if share is not None else seed) & 0xFFFFFFFF
         # scores=True: every training step ends its forward with one launch that adds the batch's counts into `self.scores`
         # (a sibling adds into its parent's table); off: no table, no launch -- the step is exactly the one without the feature
-        self.scores: Optional[ScoreTable] = None
-        if share is not None:
-            self.scores = share.scores
-        elif scores:
-            self.scores = self.new_score_table()
         # rank_scores=True: every training step also appends the softmax of its logits and its labels to `self.rank` (RankBuffer;
         # a sibling appends to its parent's), one launch where the count-table launch goes; off: no buffer, no launch
-        self.rank: Optional[RankBuffer] = None
-        self.rank_capacity = share.rank_capacity if share is not None else int(rank_capacity)
         if share is not None:
-            self.rank = share.rank
-        elif rank_scores:
-            self.rank = self.new_rank_buffer()
+            self.scores, self.rank, self.rank_capacity = share.scores, share.rank, share.rank_capacity
+        else:
+            self.rank_capacity = int(rank_capacity)
+            self.scores: Optional[ScoreTable] = self.new_score_table() if scores else None
+            self.rank: Optional[RankBuffer] = self.new_rank_buffer() if rank_scores else None
         if init and share is None:
             self.reset_parameters(seed)
         self.logits = torch.zeros(3, self.B, self.K, device=dev)
@@ -602,10 +204,8 @@ class _FlatEngine:
         if self._fused_heads:
             self._loss_weight_group["fused_heads"] = True
         self._stage_group["members"].append(weakref.ref(self))
-        if self._frozen:
-            self._enter_stage_two()                  # a sibling built after freeze_modalities()
-        if self._modal:
-            self._enter_modal_stage()                # ... after train_modalities_only()
+        if self._staged:
+            self._enter_stage()                      # a sibling built after freeze_modalities() / train_modalities_only()
         self.pack()
 
     # ---- helpers for subclasses ----------------------------------------------------------------------------
@@ -782,6 +382,19 @@ class _FlatEngine:
     def _sibling_kwargs(self) -> dict:
         return {"fusion_loss_weight": self.fusion_loss_weight} if hasattr(self, "fusion_loss_weight") else {}
 
+    def _spawn(self, batch_size: int, share):
+        """Another engine of this one's class, cfg, precision and hyper-parameters: over this engine's buffers (share=self:
+        sibling) or over fresh ones (share=None: clone)."""
+        prec = {v: k for k, v in L.PREC_BY_NAME.items() if k in ("bf16", "fp32")}[self.prec]
+        new = type(self)(self.cfg, batch_size, device=self.device, precision=prec, lr=float(self.adam_state[1]),
+                         betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, seed=self.seed, init=False,
+                         share=share, **self._sibling_kwargs())
+        self._copy_loaded_state(new)
+        return new
+
+    def _copy_loaded_state(self, new):
+        """Give `new` the non-parameter state a load_state_dict left on this engine (MM-IMDb: the criterion buffer)."""
+
     def sibling(self, batch_size: int, trains: bool = True):
         """An engine for another batch size over THIS engine's parameters, gradients, Adam state and step counters
         (constructor argument share=): the step that takes an epoch's ragged last batch, or a validation engine.
@@ -792,12 +405,7 @@ class _FlatEngine:
         so the keep flags of both are narrowed to the ranges BOTH overwrite.  A captured graph holds its range table BY VALUE
         (m2m_adam_step_ranges copies it into the kernel arguments), so narrowing after capture() would leave the graph with
         the old flags: that is refused -- build training siblings before capture(), or capture again."""
-        prec = {v: k for k, v in L.PREC_BY_NAME.items() if k in ("bf16", "fp32")}[self.prec]
-        sib = type(self)(self.cfg, batch_size, device=self.device, precision=prec, lr=float(self.adam_state[1]),
-                         betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, seed=self.seed, init=False,
-                         share=self, **self._sibling_kwargs())
-        if hasattr(self, "pos_weight"):                      # MM-IMDb: the LOADED criterion buffer, not cfg's (ADVICE r2)
-            sib.pos_weight.copy_(self.pos_weight)
+        sib = self._spawn(batch_size, share=self)
         if not trains:
             sib._eval_only = True
             return sib
@@ -811,13 +419,23 @@ class _FlatEngine:
             eng._ranges_add = [(lo, n, v, int(k and lo in other)) for lo, n, v, k in eng._ranges_add]
         return sib
 
-    # ---- stage two: frozen modality towers (models/avmnist.py:292-293, :314-324) -------------------------------------------
+    # ---- training stages (Stage): stage two with its frozen modality towers (models/avmnist.py:292-293, :314-324) and its mirror
+    # ---- image, the modalities-only stage: the unimodal models of Gradient-Blending (modules/gradblend.py:92-98) ---------------
     def _frozen_prefixes(self) -> Tuple[str, ...]:
         return frozen_key_prefixes(self.HEAD_NAMES[:2])
 
     @property
     def _frozen(self) -> bool:
-        return self._stage_group["frozen"]
+        return self._stage_group["stage"] is FROZEN
+
+    @property
+    def _modal(self) -> bool:
+        return self._stage_group["stage"] is MODAL
+
+    @property
+    def _staged(self) -> bool:
+        """In stage two or in the modalities-only stage: Adam runs per trainable range, a gradient exchange is refused."""
+        return self._stage_group["stage"] is not None
 
     def freeze_modalities(self):
         """Enter stage two of the reference's two-stage training, for this engine, its siblings and siblings built later (there
@@ -830,60 +448,10 @@ class _FlatEngine:
             alone, Adam over the trainable ranges only and the re-pack of the fusion tower only.
         Captured graphs are dropped as release_capture() drops them: capture again.  Refused with M2M_FUSED_HEADS=1 (that launch
         takes the loss weights by value); a gradient exchange is refused in stage two (single GPU)."""
-        grp = self._stage_group
-        if grp["frozen"]:
-            return
-        if grp["modal"]:
-            raise RuntimeError("freeze_modalities: this engine family is in the modalities-only stage (train_modalities_only), "
-                               "which has no way back")
-        if self._loss_weight_group["fused_heads"]:
-            raise RuntimeError("freeze_modalities: the fused heads + fusion backward launch (M2M_FUSED_HEADS=1) takes the loss "
-                               "weights by value; stage two needs that switch off")
-        grp["weights"] = torch.tensor([0.0, 0.0, 1.0], dtype=torch.float32, device=self.device)
-        grp["frozen"] = True
-        self._enter_stage(lambda m: m._enter_stage_two())
-
-    def _enter_stage(self, enter):
-        """What freeze_modalities and train_modalities_only share once the stage group is marked: clear the new stage's trainable
-        gradient ranges, let every member re-derive its launch options (enter(member)), narrow the kept gradient ranges."""
-        grp = self._stage_group
-        members = [m for m in (r() for r in grp["members"]) if m is not None]
-        grp["members"] = [weakref.ref(m) for m in members]
-        # Stage one left the ranges its overwriting weight-gradient launch owned uncleared ("keep").  A range the new stage's
-        # weight-gradient call accumulates into instead (another row plan: no slot) must start from zero: clear every trainable
-        # range once, here, outside any graph.
-        for lo, hi in trainable_flat_ranges(self.shapes, self._frozen_prefixes(), invert=grp["modal"]):
-            self.flat_g[lo:hi].zero_()
-        for m in members:
-            enter(m)
-        # one gradient buffer: a range one engine leaves uncleared must be overwritten by every other training engine (sibling())
-        trains = [m for m in members if not m._eval_only]
-        for m in trains:
-            others = [{r[0] for r in o._ranges_add} for o in trains if o is not m]
-            m._ranges_add = [(lo, n, v, int(k and all(lo in o for o in others))) for lo, n, v, k in m._ranges_add]
-
-    def _enter_stage_two(self):
-        self.release_capture()
-        self._trainable = trainable_flat_ranges(self.shapes, self._frozen_prefixes())
-        self._slots_folded = False
-        self._stage_two_options()
-
-    def _stage_two_options(self):
-        """Launch options of the stage-two step, re-derived for its own launches (subclasses)."""
-
-    def _stage_two_packs(self) -> list:
-        """The modules whose packed operand copies a stage-two update rebuilds: the fusion tower."""
-        return [self.t_fus]
-
-    # ---- the modalities-only stage: the unimodal models of Gradient-Blending (modules/gradblend.py:92-98) ----------------------
-    @property
-    def _modal(self) -> bool:
-        return self._stage_group["modal"]
-
-    @property
-    def _staged(self) -> bool:
-        """In stage two or in the modalities-only stage: Adam runs per trainable range, a gradient exchange is refused."""
-        return self._stage_group["frozen"] or self._stage_group["modal"]
+        self._enter(FROZEN, "freeze_modalities", [
+            (self._loss_weight_group["fused_heads"],
+             "freeze_modalities: the fused heads + fusion backward launch (M2M_FUSED_HEADS=1) takes the loss "
+             "weights by value; stage two needs that switch off")])
 
     def train_modalities_only(self):
         """Enter the mirror image of stage two, for this engine, its siblings and siblings built later (one-way, like the freeze):
@@ -901,54 +469,74 @@ class _FlatEngine:
         evaluate() stays the full model under `loss_weights`.  Captured graphs are dropped: capture again.  Refused with
         M2M_FUSED_HEADS=1, on engines built with scores / rank_scores (the fusion head's predictions are not produced), after
         freeze_modalities(); a gradient exchange is refused in this stage (single GPU)."""
+        self._enter(MODAL, "train_modalities_only", [
+            (self._loss_weight_group["fused_heads"],
+             "train_modalities_only: the fused heads + fusion backward launch (M2M_FUSED_HEADS=1) belongs to the "
+             "fusion tower's backward, which this stage does not run; it needs that switch off"),
+            (self.scores is not None or self.rank is not None,
+             "train_modalities_only: an engine built with scores=True / rank_scores=True counts the fusion head's "
+             "predictions on every training step; this stage does not produce them")])
+
+    def _enter(self, stage: Stage, method: str, refusals):
+        """Take the engine family into `stage` (both stages are one-way).  refusals: [(condition, message)], the entering
+        method's own, checked once the family is known to be in stage one."""
         grp = self._stage_group
-        if grp["modal"]:
+        if grp["stage"] is stage:
             return
-        if grp["frozen"]:
-            raise RuntimeError("train_modalities_only: this engine family is in stage two (freeze_modalities), which has no way back")
-        if self._loss_weight_group["fused_heads"]:
-            raise RuntimeError("train_modalities_only: the fused heads + fusion backward launch (M2M_FUSED_HEADS=1) belongs to the "
-                               "fusion tower's backward, which this stage does not run; it needs that switch off")
-        if self.scores is not None or self.rank is not None:
-            raise RuntimeError("train_modalities_only: an engine built with scores=True / rank_scores=True counts the fusion head's "
-                               "predictions on every training step; this stage does not produce them")
-        grp["weights"] = torch.tensor([1.0, 1.0, 0.0], dtype=torch.float32, device=self.device)
-        grp["modal"] = True
-        self._enter_stage(lambda m: m._enter_modal_stage())
+        if grp["stage"] is not None:
+            raise RuntimeError(f"{method}: this engine family is in {grp['stage'].title}, which has no way back")
+        for refused, message in refusals:
+            if refused:
+                raise RuntimeError(message)
+        grp["weights"] = torch.tensor(stage.weights, dtype=torch.float32, device=self.device)
+        grp["stage"] = stage
+        members = [m for m in (r() for r in grp["members"]) if m is not None]
+        grp["members"] = [weakref.ref(m) for m in members]
+        # Stage one left the ranges its overwriting weight-gradient launch owned uncleared ("keep").  A range the new stage's
+        # weight-gradient call accumulates into instead (another row plan: no slot) must start from zero: clear every trainable
+        # range once, here, outside any graph.
+        for lo, hi in trainable_flat_ranges(self.shapes, self._frozen_prefixes(), invert=stage.invert):
+            self.flat_g[lo:hi].zero_()
+        for m in members:
+            m._enter_stage()
+        # one gradient buffer: a range one engine leaves uncleared must be overwritten by every other training engine (sibling())
+        trains = [m for m in members if not m._eval_only]
+        for m in trains:
+            others = [{r[0] for r in o._ranges_add} for o in trains if o is not m]
+            m._ranges_add = [(lo, n, v, int(k and all(lo in o for o in others))) for lo, n, v, k in m._ranges_add]
 
-    def _enter_modal_stage(self):
+    def _enter_stage(self):
+        """One member's side of _enter; also what a sibling built after it does at construction."""
         self.release_capture()
-        self._trainable = trainable_flat_ranges(self.shapes, self._frozen_prefixes(), invert=True)
+        self._trainable = trainable_flat_ranges(self.shapes, self._frozen_prefixes(), invert=self._stage_group["stage"].invert)
         self._slots_folded = False
-        self._modal_stage_options()
+        self._stage_options()
 
-    def _modal_stage_options(self):
-        """Launch options of the modalities-only step, re-derived for its own launches (subclasses)."""
-
-    def _modal_stage_packs(self) -> list:
-        """The modules whose packed operand copies a modalities-only update rebuilds."""
-        raise NotImplementedError
-
-    def _modal_total(self, training: bool):
-        """Modalities-only stage, training: the two-head launch left its total in losses[2] (slot nheads).  losses[3] is written
-        as the one fp32 sum of the two heads' losses (the atomics' arrival order does not show), losses[2] is the fusion head's
-        loss, which this stage does not compute: zero."""
-        if training and self._modal:
-            torch.add(self.losses[0:1], self.losses[1:2], out=self.losses[3:4])
-            self.losses[2:3].copy_(self._stage_group["weights"][2:3])
+    def _stage_options(self):
+        """Launch options of the stage's step, re-derived for its own launches (subclasses)."""
 
     def _pass_weights(self, training: bool) -> torch.Tensor:
         """The device table of loss coefficients the heads launch of this pass reads."""
         return self._stage_group["weights"] if (training and self._staged) else self.loss_weights
 
-    def _stage_two_total(self, training: bool):
-        """Stage two, training: losses[3] = losses[2].  The heads kernel adds each workgroup's term to its head's loss and,
-        times the coefficient, to the total with two atomics; with coefficients (0, 0, 1) the total is the same terms, but three
-        or more workgroups may arrive in another order at the second address -- one 4-byte copy makes the equality exact."""
-        if training and self._frozen:
+    def _stage_total(self, training: bool):
+        """A stage's training pass: the total loss as an exact function of the heads' losses.
+        Stage two: losses[3] = losses[2].  The heads kernel adds each workgroup's term to its head's loss and, times the
+        coefficient, to the total with two atomics; with coefficients (0, 0, 1) the total is the same terms, but three or more
+        workgroups may arrive in another order at the second address -- one 4-byte copy makes the equality exact.
+        Modalities-only stage: the two-head launch left its total in losses[2] (slot nheads).  losses[3] is written as the one
+        fp32 sum of the two heads' losses (the atomics' arrival order does not show), losses[2] is the fusion head's loss, which
+        this stage does not compute: zero."""
+        if not training:
+            return
+        if self._frozen:
             self.losses[3:4].copy_(self.losses[2:3])
+        elif self._modal:
+            torch.add(self.losses[0:1], self.losses[1:2], out=self.losses[3:4])
+            self.losses[2:3].copy_(self._stage_group["weights"][2:3])
 
-    def _update_stage_two(self, grad_scale: float, grad_bf16):
+    def _update_trainable_ranges(self, grad_scale: float, grad_bf16):
+        """A stage's update: Adam over each trainable range, then the re-pack of what the stage trains."""
         if grad_bf16 is not None:
             raise RuntimeError("stage two (freeze_modalities) / the modalities-only stage is single GPU: no exchanged bf16 gradient")
         if not self._slots_folded:                   # (stage two's single-tower call has no slot; a grouped modality pair may)
@@ -957,14 +545,12 @@ class _FlatEngine:
         self._slots_folded = False
         for lo, hi in self._trainable:               # the existing range form, one launch per trainable range
             self._adam_chunk(lo, hi, grad_scale)
-        for m in (self._modal_stage_packs() if self._modal else self._stage_two_packs()):
+        for m in self._stage_packs():                # the modules whose packed operand copies this stage's update rebuilds
             m.pack(force=True)
 
-    def _refuse_exchange_when_frozen(self, grad_sync):
-        if grad_sync is not None and self._frozen:
-            raise RuntimeError("stage two (freeze_modalities) is single GPU: a grad_sync is refused")
-        if grad_sync is not None and self._modal:
-            raise RuntimeError("the modalities-only stage (train_modalities_only) is single GPU: a grad_sync is refused")
+    def _refuse_exchange_in_a_stage(self, grad_sync):
+        if grad_sync is not None and self._staged:
+            raise RuntimeError(f"{self._stage_group['stage'].title} is single GPU: a grad_sync is refused")
 
     # ---- optimizer -------------------------------------------------------------------------------------------
     def _check_grad_bf16(self, grad_bf16: Optional[torch.Tensor]):
@@ -1014,15 +600,10 @@ class _FlatEngine:
         """An INDEPENDENT engine of the same cfg, precision and hyper-parameters (default: the same batch size) that starts from a
         copy of this one's parameters and loss weights, with zero Adam moments, step count and dropout counter, in stage one, and
         without score tables or ranking buffers.  Nothing is shared with this engine (unlike sibling())."""
-        prec = {v: k for k, v in L.PREC_BY_NAME.items() if k in ("bf16", "fp32")}[self.prec]
-        new = type(self)(self.cfg, self.B if batch_size is None else int(batch_size), device=self.device, precision=prec,
-                         lr=float(self.adam_state[1]), betas=self.betas, eps=self.eps, weight_decay=self.weight_decay, seed=self.seed,
-                         init=False, **self._sibling_kwargs())
+        new = self._spawn(self.B if batch_size is None else int(batch_size), share=None)
         new.flat_p.copy_(self.flat_p)
         new.loss_weights.copy_(self.loss_weights)
         new.head_weights = dict(self.head_weights)
-        if hasattr(self, "pos_weight"):
-            new.pos_weight.copy_(self.pos_weight)
         new.pack()
         return new
 
@@ -1050,9 +631,11 @@ class _FlatEngine:
         # Adam skip the slot of the two-group tower: the slot is folded by forward_backward only)
         self._slots_folded = False
         self._forward(*batch, training=True, with_grad=True, prologue=True)
-        self._score_forward(batch[-1])
+        if not self._fused_heads:                    # the training forward left `preds` and `logits` written
+            self._score_add(batch[-1])
         self._backward(*batch[:-1], fused_update=fused_update)
-        self._score_backward(batch[-1])
+        if self._fused_heads:                        # the heads rode in the fusion tower's backward launch
+            self._score_add(batch[-1])
 
     # ---- scores ----------------------------------------------------------------------------------------------
     def new_score_table(self) -> ScoreTable:
@@ -1062,26 +645,20 @@ class _FlatEngine:
     def score_table(self, split: str) -> ScoreTable:
         """The table of `split`, kept on the engine: "train" is the training table (`self.scores`, which needs scores=True),
         any other name gets a table of its own on first use."""
+        return self._of_split(split, self.scores, "_split_scores", self.new_score_table,
+                              "score_table('train'): this engine was built with scores=False")
+
+    def _of_split(self, split: str, training, attr: str, new, refusal: str):
+        """score_table / rank_buffer: `training` for "train" (refused when the engine was built without it), else the split's own
+        accumulator, made by new() on first use and kept in the dict `attr` (which exists from the first such use on)."""
         if split == "train":
-            if self.scores is None:
-                raise RuntimeError("score_table('train'): this engine was built with scores=False")
-            return self.scores
-        tables = self.__dict__.setdefault("_split_scores", {})
-        if split not in tables:
-            tables[split] = self.new_score_table()
-        return tables[split]
-
-    def _preds_in_forward(self) -> bool:
-        """Whether a training forward leaves `preds` written (False: the heads ride in the fusion tower's backward launch)."""
-        return not self._fused_heads
-
-    def _score_forward(self, truth):
-        if self._preds_in_forward():
-            self._score_add(truth)
-
-    def _score_backward(self, truth):
-        if not self._preds_in_forward():
-            self._score_add(truth)
+            if training is None:
+                raise RuntimeError(refusal)
+            return training
+        kept = self.__dict__.setdefault(attr, {})
+        if split not in kept:
+            kept[split] = new()
+        return kept[split]
 
     def _score_add(self, truth):
         """Behind the launch that writes `preds` and `logits`: the count-table launch and / or the ranking append."""
@@ -1089,6 +666,18 @@ class _FlatEngine:
             self.scores.add(self.preds, truth)
         if self.rank is not None:
             self.rank.add(self.logits, truth)
+
+    @torch.no_grad()
+    def evaluate(self, *batch, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None):
+        """validation/test step on `batch` (the inputs, then the labels): dropout off (the reference's shared_step under
+        model.eval()).  scores: a table (new_score_table / score_table(split)) this batch's counts are added into.  rank: a
+        ranking buffer (new_rank_buffer / rank_buffer(split)) this batch's softmax rows are appended to."""
+        self._forward(*batch, False, False)
+        if scores is not None:
+            scores.add(self.preds, batch[-1])
+        if rank is not None:
+            rank.add(self.logits, batch[-1])
+        return self._eval_outputs()                  # views of `logits` / `losses` / `preds` under the reference's names
 
     # ---- ranking buffers -------------------------------------------------------------------------------------
     def new_rank_buffer(self) -> RankBuffer:
@@ -1098,14 +687,8 @@ class _FlatEngine:
     def rank_buffer(self, split: str) -> RankBuffer:
         """The buffer of `split`, kept on the engine: "train" is the training buffer (`self.rank`, which needs
         rank_scores=True), any other name gets a buffer of its own on first use."""
-        if split == "train":
-            if self.rank is None:
-                raise RuntimeError("rank_buffer('train'): this engine was built with rank_scores=False")
-            return self.rank
-        buffers = self.__dict__.setdefault("_split_ranks", {})
-        if split not in buffers:
-            buffers[split] = self.new_rank_buffer()
-        return buffers[split]
+        return self._of_split(split, self.rank, "_split_ranks", self.new_rank_buffer,
+                              "rank_buffer('train'): this engine was built with rank_scores=False")
 
     def _check_trains(self):
         if self._eval_only:
@@ -1130,7 +713,7 @@ class _FlatEngine:
         """Adam over every parameter + operand re-pack.  One launch (m2m_adam_pack_all) where the model allows it: the
         re-pack then takes the updated weights from the workgroup that computed them instead of re-reading the masters."""
         if self._staged:
-            self._update_stage_two(grad_scale, grad_bf16)
+            self._update_trainable_ranges(grad_scale, grad_bf16)
             return
         mods = self._adam_pack_modules() if self._fused_update else None
         # the slot of a two-group tower: added inside Adam (fused step) unless forward_backward has folded it in already
@@ -1164,7 +747,7 @@ class _FlatEngine:
         exchange (the whole step when there is none); update(k, scale): the update behind the exchange -- of chunk k of
         _update_chunks() when pipelined (chunk k + 1 .. are still on the communication stream), else k = 0: everything.
         Eager steps pass _phases(), a captured step its graphs' replays."""
-        self._refuse_exchange_when_frozen(grad_sync)
+        self._refuse_exchange_in_a_stage(grad_sync)
         mode = _exchange_mode(grad_sync)
         first()
         if mode == "none":
@@ -1234,64 +817,28 @@ class _FlatEngine:
         capture() does not train: the warm-up steps it needs are undone (parameters, Adam moments, step counters)."""
         if steps < 1 or (steps > 1 and grad_sync is not None):
             raise ValueError("steps > 1 is only supported without a gradient exchange")
-        self._refuse_exchange_when_frozen(grad_sync)
+        self._refuse_exchange_in_a_stage(grad_sync)
         nb = len(batch)
         slots = [tuple(t.clone() for t in batch) for _ in range(steps)]
         if steps > 1 and config.switch_on("M2M_CAPTURE_SHARE_SLOTS"):
             slots = [slots[0]] * steps                  # diagnostic (scripts/spg_probe.sh): every step reads the SAME (cache-resident) batch
         self._static = slots[0] if steps == 1 else slots
-        st = slots[0]
-        # The warm-up below runs REAL training steps (lazy initialisation of the launches must happen outside the capture).
-        # Everything they change is put back afterwards, so capture() leaves the model exactly as it found it.
-        state = [self.flat_p, self.flat_m, self.flat_v, self.flat_g, self.adam_state, self.drop_step]
-        if self.scores is not None:
-            state.append(self.scores.table)          # (the warm-up steps count their batch too)
-        if self.rank is not None:
-            state.append(self.rank.state)            # (... and append it: the cursor goes back, the rows behind it are dead)
-        snap = [t.clone() for t in state]
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            first, update = self._phases(st, grad_sync)
-            for _ in range(2):                       # warm-up: lazy inits (LDS attributes, allocations) happen here
-                scale = self._run_step(grad_sync, first, update)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        for dst, src in zip(state, snap):
-            dst.copy_(src)
-        self.pack()
-        torch.cuda.synchronize()
+        first, update = self._phases(slots[0], grad_sync)
+        scale = self._undo_warmup(lambda: self._run_step(grad_sync, first, update))
+        with self._per_step_outputs(steps) as (outs, enter):
+            if steps > 1:
+                self.losses_steps, self.logits_steps, self.preds_steps = outs
 
-        def graph_of(fn):
-            # thread_local capture mode: a data-parallel process has other threads (the RCCL watchdog) that may touch the HIP
-            # runtime while this thread captures; only this thread's calls belong to the graph
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
-                fn()
-            return g
+                def first():
+                    for i in range(steps):
+                        enter(i)
+                        self.fused_step(*slots[i])
 
-        out_losses = self.losses
-        if steps > 1:
-            # per-step output slots of THIS graph; the engine's own losses / logits / preds stay what they were (other
-            # captured graphs and evaluate() write those)
-            home = (self.losses, self.logits, self.preds)
-            self.losses_steps = torch.zeros(steps, *self.losses.shape, device=self.device)
-            self.logits_steps = torch.zeros(steps, *self.logits.shape, device=self.device)
-            self.preds_steps = torch.zeros(steps, *self.preds.shape, dtype=self.preds.dtype, device=self.device)
-            out_losses = self.losses_steps
-
-            def all_steps():
-                for i in range(steps):
-                    self.losses, self.logits, self.preds = self.losses_steps[i], self.logits_steps[i], self.preds_steps[i]
-                    self.fused_step(*slots[i])
-
-            first = all_steps
-        # forward + backward (no exchange: the whole step, `steps` times) | [the all-reduce lands] Adam + re-pack: one graph, or one
-        # small graph per chunk when pipelined (the scale, and a bf16 exchange's buffer, exist since the warm-up)
-        nupd = {"none": 0, "single": 1, "pipelined": len(self._update_chunks())}[_exchange_mode(grad_sync)]
-        graphs = (graph_of(first), *[graph_of(lambda k=k: update(k, scale)) for k in range(nupd)])
-        if steps > 1:
-            self.losses, self.logits, self.preds = home
+            # forward + backward (no exchange: the whole step, `steps` times) | [the all-reduce lands] Adam + re-pack: one graph, or
+            # one small graph per chunk when pipelined (the scale, and a bf16 exchange's buffer, exist since the warm-up)
+            nupd = {"none": 0, "single": 1, "pipelined": len(self._update_chunks())}[_exchange_mode(grad_sync)]
+            graphs = (self._graph_of(first), *[self._graph_of(lambda k=k: update(k, scale)) for k in range(nupd)])
+        out_losses = self.losses if outs is None else outs[0]
         self._slots_folded = False
         self._graph = graphs
 
@@ -1307,6 +854,59 @@ class _FlatEngine:
 
         replay.losses = out_losses
         return replay
+
+    def _undo_warmup(self, step, extra_state: Sequence[torch.Tensor] = ()):
+        """Run step() twice on a side stream and put back what it changed; returns the second call's value.  The warm-up runs
+        REAL training steps (lazy initialisation of the launches -- LDS attributes, allocations -- must happen outside the
+        capture); everything they change is restored afterwards, so a capture leaves the model exactly as it found it.
+        extra_state: the tensors a caller's step changes beyond the engine's own (a feed's cursor and accumulators)."""
+        state = [self.flat_p, self.flat_m, self.flat_v, self.flat_g, self.adam_state, self.drop_step, *extra_state]
+        if self.scores is not None:
+            state.append(self.scores.table)          # (the warm-up steps count their batch too)
+        if self.rank is not None:
+            state.append(self.rank.state)            # (... and append it: the cursor goes back, the rows behind it are dead)
+        snap = [t.clone() for t in state]
+        s = torch.cuda.Stream(device=self.device)
+        s.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(s):
+            for _ in range(2):
+                out = step()
+        torch.cuda.current_stream().wait_stream(s)
+        torch.cuda.synchronize()
+        for dst, src in zip(state, snap):
+            dst.copy_(src)
+        self.pack()
+        torch.cuda.synchronize()
+        return out
+
+    @contextmanager
+    def _per_step_outputs(self, steps: int):
+        """The output slots of ONE captured graph of `steps` steps.  Yields (outs, enter): outs = (losses, logits, preds), each
+        with a leading `steps` axis, or None for a single step; enter(i) points self.losses / logits / preds at slot i for the
+        step captured next.  On the way out, capture error or not, the engine's own buffers are back: they stay what they were
+        (other captured graphs and evaluate() write those)."""
+        home = (self.losses, self.logits, self.preds)
+        outs = None
+        if steps > 1:
+            outs = tuple(torch.zeros(steps, *t.shape, dtype=t.dtype, device=self.device) for t in home)
+
+        def enter(i):
+            if outs is not None:
+                self.losses, self.logits, self.preds = (t[i] for t in outs)
+
+        try:
+            yield outs, enter
+        finally:
+            self.losses, self.logits, self.preds = home
+
+    @staticmethod
+    def _graph_of(fn):
+        # thread_local capture mode: a data-parallel process has other threads (the RCCL watchdog) that may touch the HIP
+        # runtime while this thread captures; only this thread's calls belong to the graph
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, capture_error_mode="thread_local"):
+            fn()
+        return g
 
     def capture_feed(self, feed: EpochFeed, steps: int = 1, grad_sync=None):
         """Capture `steps` consecutive training steps that feed themselves from `feed` (EpochFeed); returns a callable replay()
@@ -1332,43 +932,17 @@ class _FlatEngine:
             self.fused_step(*slots[i])
             feed.accumulate(self, slots[i][-1])
 
-        # as capture(): the warm-up runs REAL steps; everything they change is put back -- here the feed's state too
-        state = [self.flat_p, self.flat_m, self.flat_v, self.flat_g, self.adam_state, self.drop_step, feed.state, feed._acc]
-        if feed.mute_state is not None:
-            state.append(feed.mute_state)            # (the warm-up gathers advance the muting schedule's step index too)
-        if self.scores is not None:
-            state.append(self.scores.table)
-        if self.rank is not None:
-            state.append(self.rank.state)
-        snap = [t.clone() for t in state]
-        s = torch.cuda.Stream(device=self.device)
-        s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):
-            for _ in range(2):
-                fed_step(0)
-        torch.cuda.current_stream().wait_stream(s)
-        torch.cuda.synchronize()
-        for dst, src in zip(state, snap):
-            dst.copy_(src)
-        self.pack()
-        torch.cuda.synchronize()
-
-        out_losses = self.losses
-        home = (self.losses, self.logits, self.preds)
-        if steps > 1:                                   # per-step output slots of THIS graph, as capture(steps > 1)
-            losses_steps = torch.zeros(steps, *self.losses.shape, device=self.device)
-            logits_steps = torch.zeros(steps, *self.logits.shape, device=self.device)
-            preds_steps = torch.zeros(steps, *self.preds.shape, dtype=self.preds.dtype, device=self.device)
-            out_losses = losses_steps
-        g = torch.cuda.CUDAGraph()
-        try:
-            with torch.cuda.graph(g, capture_error_mode="thread_local"):
+        # (the warm-up gathers advance the muting schedule's step index too)
+        mute = [] if feed.mute_state is None else [feed.mute_state]
+        self._undo_warmup(lambda: fed_step(0), [feed.state, feed._acc, *mute])
+        with self._per_step_outputs(steps) as (outs, enter):
+            def all_steps():
                 for i in range(steps):
-                    if steps > 1:
-                        self.losses, self.logits, self.preds = losses_steps[i], logits_steps[i], preds_steps[i]
+                    enter(i)
                     fed_step(i)
-        finally:
-            self.losses, self.logits, self.preds = home
+
+            g = self._graph_of(all_steps)
+        out_losses = self.losses if outs is None else outs[0]
         self._slots_folded = False
         self._graph = (g,)
 
@@ -1378,7 +952,7 @@ class _FlatEngine:
 
         replay.losses, replay.slots, replay.steps, replay.feed = out_losses, slots, steps, feed
         if steps > 1:
-            replay.logits, replay.preds = logits_steps, preds_steps
+            replay.logits, replay.preds = outs[1], outs[2]
         return replay
 
 
@@ -1472,12 +1046,8 @@ class _TwoTowerEngine(_FlatEngine):
             self._embed_towers = [self.t_a, self.t_b]
             # their weight gradients are then written ("="), and Adam leaves those ranges uncleared -- if the range table has room
             fast = bool(L.lib().m2m_embeds_wgrad_form(_embed_ptrs(self._embeds), _tower_ptrs(self._embed_towers), 2, B))
-            if fast and config.switch_on("M2M_WGRAD_OVERWRITE") and len(self._ranges_add) + 2 <= L.MAX_GRAD_RANGES:
-                for e, pre in ((self.e_a, f"{a}_mixer."), (self.e_b, f"{b}_mixer.")):
-                    gw = self.grads[pre + "to_patch_embedding.0.weight"]
-                    e.set_wgrad_overwrite(True)
-                    self._ranges_add.append(((gw.data_ptr() - self.flat_g.data_ptr()) // 4, gw.numel(), None, 1))
-                self._ranges_add.sort(key=lambda r: r[0])
+            if fast and config.switch_on("M2M_WGRAD_OVERWRITE"):
+                self._keep_embed_ranges(self._embed_weight_grads())
 
         # Patch embeddings inside the two-tower forward launch (m2m_towers_forward_embeds: -1 launch at the head of the step).
         # The step head then splits: losses = 0 / Adam step += 1 ride in that launch, the dropout counter -- which that launch
@@ -1635,7 +1205,7 @@ class _TwoTowerEngine(_FlatEngine):
             heads[2]["tokens"] = (self.fus_out, self.Nf, fs)
         self._wgrad_heads = None
         if modal:
-            heads = heads[:2]                              # (their total lands in losses[2]: _modal_total)
+            heads = heads[:2]                              # (their total lands in losses[2]: _stage_total)
         if training and with_grad and self._head_part is not None and not self._staged:
             # (a stage: its weight-gradient call adds no slots; the heads add with atomics)
             for i, h in enumerate(heads):
@@ -1646,8 +1216,7 @@ class _TwoTowerEngine(_FlatEngine):
         if training and with_grad and self._fused_heads:
             return                                         # heads + losses ride in the fusion tower's backward launch (_backward)
         self._loss_heads(heads, labels, not training)      # a training step's _prologue already cleared the losses
-        self._stage_two_total(training)
-        self._modal_total(training)
+        self._stage_total(training)
 
     def _backward(self, xa, xb, fused_update: bool = False):
         """Backward of the whole model.  fused_update: also apply Adam + re-pack (single-GPU path; with a gradient
@@ -1727,32 +1296,36 @@ class _TwoTowerEngine(_FlatEngine):
         if fused_update:
             self._update(1.0)
 
-    def _stage_two_options(self):
-        """The options _setup_wgrad chose for the grouped weight-gradient launch (the fusion tower's slot, overwrite decided with
-        the slot in hand, the embeddings' kept ranges) re-derived for the single-tower call of stage two."""
-        self.t_fus.set_wgrad_overwrite(False)
-        self._setup_wgrad([[self.t_fus]])
+    def _embed_weight_grads(self) -> list:
+        """[(patch embedding, its weight's gradient view)] of the two modalities."""
+        return [(e, self.grads[f"{m}_mixer.to_patch_embedding.0.weight"]) for e, m in zip(self._embeds, self.MODS)]
 
-    def _modal_stage_options(self):
-        """The same re-derivation for the modalities-only stage's weight-gradient launch: the two modality towers and their
-        embeddings, without the fusion tower (whose slot and kept ranges leave the table).  The embeddings keep their
-        single-owner ("=") form and their uncleared ranges where the table still has room; else they go back to adding."""
-        for t in (self.t_a, self.t_b, self.t_fus):
-            t.set_wgrad_overwrite(False)
-        self._setup_wgrad([[self.t_a, self.t_b]])
-        a, b = self.MODS
-        owned = [(e, self.grads[pre + "to_patch_embedding.0.weight"]) for e, pre in ((self.e_a, f"{a}_mixer."), (self.e_b, f"{b}_mixer."))
-                 if e.desc.wgrad_flags & L.WGRAD_OVERWRITE]
-        if owned and len(self._ranges_add) + len(owned) > L.MAX_GRAD_RANGES:
-            for e, _ in owned:
-                e.set_wgrad_overwrite(False)
-            owned = []
-        for _, gw in owned:
-            self._ranges_add.append(((gw.data_ptr() - self.flat_g.data_ptr()) // 4, gw.numel(), None, 1))
+    def _keep_embed_ranges(self, owners: list):
+        """Enter the weight-gradient ranges of embeddings that can run in their single-owner form into _ranges_add (owners: of
+        _embed_weight_grads): the gradients are then written ("="), and Adam leaves those ranges uncleared -- if the range table
+        has room for all of them; else the embeddings add into cleared ranges like everything else."""
+        fits = len(self._ranges_add) + len(owners) <= L.MAX_GRAD_RANGES
+        for e, gw in owners:
+            e.set_wgrad_overwrite(fits)
+            if fits:
+                self._ranges_add.append(((gw.data_ptr() - self.flat_g.data_ptr()) // 4, gw.numel(), None, 1))
         self._ranges_add.sort(key=lambda r: r[0])
 
-    def _modal_stage_packs(self) -> list:
-        return [self.t_a, self.e_a, self.t_b, self.e_b]
+    def _stage_options(self):
+        """The options _build chose for the grouped weight-gradient launch (the fusion tower's slot, overwrite decided with the
+        slot in hand, the embeddings' kept ranges) re-derived for the stage's own launch: the single-tower call of stage two, or
+        the two modality towers and their embeddings without the fusion tower, whose slot and kept ranges leave the table."""
+        towers = [self.t_fus] if self._frozen else [self.t_a, self.t_b]
+        for t in dict.fromkeys(towers + [self.t_fus]):       # (a fusion tower that leaves the launch gives up its ranges too)
+            t.set_wgrad_overwrite(False)
+        self._setup_wgrad([towers])
+        if not self._frozen:
+            # the embeddings' gradients ride in their towers' launch: they keep their single-owner form and their uncleared
+            # ranges where the table still has room
+            self._keep_embed_ranges([(e, gw) for e, gw in self._embed_weight_grads() if e.desc.wgrad_flags & L.WGRAD_OVERWRITE])
+
+    def _stage_packs(self) -> list:
+        return [self.t_fus] if self._frozen else [self.t_a, self.e_a, self.t_b, self.e_b]
 
     def _update_chunks(self):
         """One chunk per parameter segment, in flat order: modality a (its patch embedding + tower), modality b, fusion tower
@@ -1762,16 +1335,7 @@ class _TwoTowerEngine(_FlatEngine):
         segs = sorted(self.segments.items(), key=lambda kv: kv[1][0])
         return [(lo, hi, mods[name]) for name, (lo, hi) in segs]
 
-    @torch.no_grad()
-    def evaluate(self, xa, xb, labels, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None):
-        """validation/test step: dropout off (the reference's shared_step under model.eval()).  scores: a table
-        (new_score_table / score_table(split)) this batch's counts are added into.  rank: a ranking buffer (new_rank_buffer /
-        rank_buffer(split)) this batch's softmax rows are appended to."""
-        self._forward(xa, xb, labels, False, False)
-        if scores is not None:
-            scores.add(self.preds, labels)
-        if rank is not None:
-            rank.add(self.logits, labels)
+    def _eval_outputs(self) -> dict:
         a, b = self.MODS
         return {"logits": self.logits[2], f"{a}_logits": self.logits[0], f"{b}_logits": self.logits[1],
                 f"loss_{a}": self.losses[0], f"loss_{b}": self.losses[1], "loss_fusion": self.losses[2],
@@ -1864,11 +1428,14 @@ class AVMnistUQEngine(AVMnistEngine):
         return True                                           # m2m_heads_edl keeps m2m_heads_ce's g_part contract
 
     @torch.no_grad()
-    def evaluate(self, xa, xb, labels, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None):
+    def evaluate(self, *batch, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None):
         """AVMnistEngine.evaluate; `preds` is the combined prediction, and the three uncertainties (B) are returned as well."""
         if rank is not None:
             raise RuntimeError("AVMnistUQEngine: ranking buffers are not built for the evidential model")
-        out = super().evaluate(xa, xb, labels, scores=scores)
+        return super().evaluate(*batch, scores=scores)
+
+    def _eval_outputs(self) -> dict:
+        out = super()._eval_outputs()
         out.update(uncertainty=self.uncertainty[2], uncertainty_image=self.uncertainty[0], uncertainty_audio=self.uncertainty[1])
         return out
 
@@ -1909,6 +1476,9 @@ class MMIMDBEngine(_TwoTowerEngine):
 
     def _extra_state(self):
         return OrderedDict((k, self.pos_weight.detach().clone()) for k in self.EXTRA_STATE_KEYS)
+
+    def _copy_loaded_state(self, new):
+        new.pos_weight.copy_(self.pos_weight)            # the LOADED criterion buffer, not cfg's
 
     def _preds_shape(self):
         return (3, self.B, self.K)
@@ -2029,11 +1599,10 @@ class MimicEngine(_FlatEngine):
             heads[1]["tokens"] = (time_part.data_ptr(), self.Nt, fs)
             heads[2]["tokens"] = (self.fus_out, self.Nf, fs)
         if modal:
-            heads = heads[:2]                               # (their total lands in losses[2]: _modal_total)
+            heads = heads[:2]                               # (their total lands in losses[2]: _stage_total)
         heads_ce(heads, labels, B, D, self.K, out=(self.logits, self.losses, self.preds), zero_losses=not training,
                  weights=self._pass_weights(training))
-        self._stage_two_total(training)
-        self._modal_total(training)
+        self._stage_total(training)
 
     def _backward(self, static, time, fused_update: bool = False):
         B, D = self.B, self.D
@@ -2096,16 +1665,11 @@ class MimicEngine(_FlatEngine):
         main.wait_stream(s_b)
         main.wait_stream(s_f)
 
-    def _modal_stage_packs(self) -> list:
-        return [self.t_time, self.e_time]                   # (the static MLP reads the fp32 masters: no packed copies)
+    def _stage_packs(self) -> list:
+        # (the static MLP reads the fp32 masters: no packed copies)
+        return [self.t_fus] if self._frozen else [self.t_time, self.e_time]
 
-    @torch.no_grad()
-    def evaluate(self, static, time, labels, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None):
-        self._forward(static, time, labels, False, False)
-        if scores is not None:
-            scores.add(self.preds, labels)
-        if rank is not None:
-            rank.add(self.logits, labels)
+    def _eval_outputs(self) -> dict:
         return {"logits": self.logits[2], "logits_static": self.logits[0], "logits_time": self.logits[1],
                 "loss_static": self.losses[0], "loss_time": self.losses[1], "loss_fusion": self.losses[2],
                 "loss": self.losses[3], "preds": self.preds[2]}

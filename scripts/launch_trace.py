@@ -3,8 +3,8 @@
 buffers the steps leave behind.  The tool a change of the Python host layer (engine.py, runtime.py) is verified with: two trees
 whose traces and hashes agree enqueue the same work with the same arguments.
 
-    python scripts/launch_trace.py --model avmnist_B --precision bf16 --batch 512 [--fusion SumFusion] [--out trace.txt]
-                                   [--dump buffers.pt]
+    python scripts/launch_trace.py --model avmnist_B --precision bf16 --batch 512 [--scenario base|stages|feed]
+                                   [--fusion SumFusion] [--out trace.txt] [--dump buffers.pt]
     PYTHONPATH=<another tree> M2M_LIB_PATH=<this tree's libm2mixer.so> python scripts/launch_trace.py ...    (the other side)
 
 The M2M_* switches under test come from the environment.  Every function of _lib.SIGNATURES is wrapped on the loaded CDLL.  A
@@ -14,10 +14,24 @@ Pointers are reduced to NULL / set, or to `flat_p+<element offset>` (flat_g, fla
 engine's four flat buffers.  Left out: the plan bytes of m2m_adam_pack_all (the layout is private to the library; the plan is
 written by m2m_adam_pack_plan_ranges, whose arguments are traced in full, so it is a function of traced values and pointers).
 
-One invocation: construct the engine (tests/golden/gen_util.py configs, seeded batch), load_state_dict(seeded make_params), two
-fused_step, forward_backward + optimizer_step(1.0), train_step(grad_sync=lambda g: 1.0), train_step(grad_sync=
-PipelinedGradSync()), evaluate, capture() + two replays, sibling(B - 3) + one train_step on it.  Only names that exist since the
-engines have siblings and the pipelined exchange are used.
+One invocation runs one scenario (--scenario) on engines built from tests/golden/gen_util.py configs with seeded batches and
+load_state_dict(seeded make_params):
+  base    (the default; its output has not changed since the tool exists, old records stay comparable) two fused_step,
+          forward_backward + optimizer_step(1.0), train_step(grad_sync=lambda g: 1.0), train_step(grad_sync=
+          PipelinedGradSync()), evaluate, capture() + two replays, sibling(B - 3) + one train_step on it.  Only names that exist
+          since the engines have siblings and the pipelined exchange are used.
+  stages  two fused_step, capture() + one replay, sibling(B - 3), freeze_modalities(), two fused_step, forward_backward +
+          optimizer_step(1.0), capture() + two replays, a sibling built after the freeze + one step on it, evaluate; then on a
+          fresh engine one fused_step, train_modalities_only(), two fused_step, probe(), capture() + one replay, evaluate,
+          clone() + one fused_step on the clone.
+  feed    an engine with scores=True (rank_scores=True where the class builds ranking buffers): an EpochFeed over 2 * B + 5
+          seeded rows, the tail's training sibling, capture_feed(steps=2), start(order), one replay, a fed step on the sibling,
+          feed.read(), evaluate into the tables of "val"; then on a fresh engine freeze_modalities(), a feed with muting=True,
+          start(order, muting=codes), capture_feed(steps=1), two replays.
+A scenario's second engine (and a clone) has flat buffers of its own: from its construction on pointers are named after those
+(the clone's as clone.flat_p+<offset>).  The sha256 block holds, per engine of the scenario, the seven buffers of the base
+scenario (+ `uncertainty` on the evidential engine) and what the scenario adds: score tables, ranking state, the feed's state,
+accumulators and muting state.  stages and feed use names that exist since GradBlend (probe, clone, train_modalities_only).
 """
 import argparse
 import ctypes as C
@@ -54,6 +68,7 @@ COUNTS = {
     "m2m_embeds_wgrad": {0: 3, 1: 3, 2: 3},
     "m2m_embeds_forward": {0: 5, 1: 5, 2: 5, 3: 5, 4: 5},
     "m2m_heads_ce": {0: 1}, "m2m_heads_bce": {0: 1}, "m2m_heads_ce_w": {0: 1}, "m2m_heads_bce_w": {0: 1},
+    "m2m_heads_edl": {0: 1}, "m2m_feed_gather": {0: 1}, "m2m_feed_gather_muted": {0: 1},
     "m2m_adam_pack_plan": {0: 1, 2: 3},
     "m2m_adam_pack_plan_ranges": {0: 1, 2: 3, 16: 17},
     "m2m_adam_pack_all": {0: 1, 2: 3},
@@ -126,7 +141,7 @@ def enc_arg(name, i, arg, ctype, args):
 
 class Recorder:
     def __init__(self, out):
-        self.out, self.flat, self.pending = out, None, []
+        self.out, self.flat, self.pending, self.held = out, None, [], []
 
     def install(self):
         lib = L.lib()
@@ -152,8 +167,14 @@ class Recorder:
             self.out.write(f"{name}({', '.join(self.fmt(r) for r in rec)}) -> {rc!r}\n")
         self.out.flush()
 
-    def set_flat(self, eng):
-        self.flat = [(k, getattr(eng, k).data_ptr(), getattr(eng, k).numel() * 4) for k in ("flat_p", "flat_g", "flat_m", "flat_v")]
+    def hold(self):
+        """Queue what follows until the next set_flat: an engine with flat buffers of its own is about to be built."""
+        self.held, self.flat = self.flat, None
+
+    def set_flat(self, eng, tag="", keep=False):
+        """Name `eng`'s flat buffers (`tag` in front) and write out what was queued; keep: beside the ones named before hold()."""
+        self.flat = (self.held if keep else []) + [(tag + k, getattr(eng, k).data_ptr(), getattr(eng, k).numel() * 4)
+                                                   for k in ("flat_p", "flat_g", "flat_m", "flat_v")]
         pending, self.pending = self.pending, []
         for item in pending:
             self.emit(item)
@@ -174,9 +195,11 @@ class Recorder:
         return repr(r)
 
 
-def build(args):
+def build(args, **kw):
     name, dev = args.model, torch.device("cuda:0")
-    if name.startswith("avmnist_"):
+    if name == "avmnist_uq":
+        cfg, cls, shapes_of, batch_of = dict(G.AVMNIST["S"]), E.AVMnistUQEngine, E.avmnist_param_shapes, G.avmnist_batch
+    elif name.startswith("avmnist_"):
         cfg = dict(G.AVMNIST[name.split("_")[1]])
         cls, shapes_of, batch_of = E.AVMnistEngine, E.avmnist_param_shapes, G.avmnist_batch
     elif name == "mmimdb":
@@ -193,30 +216,36 @@ def build(args):
         if args.fusion == "BiModalGatedUnit":
             mm.update(mod1_in=mm["hidden_dim"], mod2_in=mm["hidden_dim"], out_size=mm["hidden_dim"])
         cfg["multimodal"] = mm
-    eng = cls(cfg, args.batch, device=dev, precision=args.precision, init=False)
+    eng = cls(cfg, args.batch, device=dev, precision=args.precision, init=False, **kw)
     params = G.make_params(shapes_of(cfg), args.seed)
-    batch = tuple(t.to(dev) for t in batch_of(args.batch, args.seed + 1, cfg))
-    return eng, params, batch
+    rows = lambda n, seed: tuple(t.to(dev) for t in batch_of(n, seed, cfg))       # n seeded samples, as the engine's batch
+    return eng, params, rows(args.batch, args.seed + 1), rows
 
 
-def main():
-    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
-    ap.add_argument("--model", required=True, help="avmnist_S | avmnist_M | avmnist_B | mmimdb | mimic")
-    ap.add_argument("--precision", default="bf16")
-    ap.add_argument("--batch", type=int, required=True)
-    ap.add_argument("--fusion", default=None, help="multimodal.fusion_function of a two-tower model")
-    ap.add_argument("--dropout", type=float, default=None)
-    ap.add_argument("--seed", type=int, default=11)
-    ap.add_argument("--out", default=None, help="file for the trace (default: stdout)")
-    ap.add_argument("--dump", default=None, help="also torch.save the hashed buffers here (for a max-abs-difference comparison)")
-    args = ap.parse_args()
-    out = open(args.out, "w") if args.out else sys.stdout
-    rec = Recorder(out)
-    rec.install()
+ENGINE_BUFFERS = ("flat_p", "flat_m", "flat_v", "flat_g", "losses", "logits", "preds")
+
+
+def engine_buffers(eng, tag=""):
+    """The buffers a scenario hashes for one engine, on the host: the seven of the base scenario, `uncertainty` where it exists."""
+    keys = ENGINE_BUFFERS + (("uncertainty",) if hasattr(eng, "uncertainty") else ())
+    return {tag + k: getattr(eng, k).detach().cpu() for k in keys}
+
+
+def captured(rec, eng, batch, replays, what="capture"):
+    """capture() + `replays` replays, then the graph is let go (a training sibling may narrow the kept gradient ranges)."""
+    rec.emit("# " + what)
+    replay = eng.capture(*batch)
+    for i in range(replays):
+        rec.emit(f"# replay {i}")
+        replay(*batch)
+    torch.cuda.synchronize()
+    eng.release_capture()
+
+
+def scenario_base(rec, args):
     phase = lambda s: rec.emit("# " + s)
-
     phase("construct")
-    eng, params, batch = build(args)
+    eng, params, batch, _ = build(args)
     rec.set_flat(eng)
     phase("load_state_dict")
     eng.load_state_dict(params)
@@ -232,21 +261,187 @@ def main():
     eng.train_step(*batch, grad_sync=parallel.PipelinedGradSync())
     phase("evaluate")
     eng.evaluate(*batch)
-    phase("capture")
-    replay = eng.capture(*batch)
-    for i in range(2):
-        phase(f"replay {i}")
-        replay(*batch)
-    torch.cuda.synchronize()
-    eng.release_capture()                                        # (a training sibling may narrow the kept gradient ranges)
+    captured(rec, eng, batch, 2)
     phase(f"sibling({args.batch - 3})")
     nb = args.batch - 3
     sib = eng.sibling(nb)
     phase("sibling train_step")
     sib.train_step(*(t[:nb].contiguous() for t in batch))
     torch.cuda.synchronize()
-    phase("sha256")
-    bufs = {k: getattr(eng, k).detach().cpu() for k in ("flat_p", "flat_m", "flat_v", "flat_g", "losses", "logits", "preds")}
+    return {k: getattr(eng, k).detach().cpu() for k in ENGINE_BUFFERS}
+
+
+def scenario_stages(rec, args):
+    """Both training stages, each on an engine of its own: the stage entered with a sibling alive and a graph captured, eager and
+    captured staged steps, engines built after the stage was entered, evaluate, probe() and clone()."""
+    phase = lambda s: rec.emit("# " + s)
+    cut = lambda batch, n: tuple(t[:n].contiguous() for t in batch)
+    phase("construct")
+    eng, params, batch, _ = build(args)
+    rec.set_flat(eng)
+    phase("load_state_dict")
+    eng.load_state_dict(params)
+    for i in range(2):
+        phase(f"fused_step {i}")
+        eng.fused_step(*batch)
+    captured(rec, eng, batch, 1)
+    phase(f"sibling({args.batch - 3})")
+    before = eng.sibling(args.batch - 3)                         # alive at the freeze: it re-enters the stage with the engine
+    phase("freeze_modalities")
+    eng.freeze_modalities()
+    for i in range(2):
+        phase(f"frozen fused_step {i}")
+        eng.fused_step(*batch)
+    phase("frozen forward_backward + optimizer_step(1.0)")
+    eng.forward_backward(*batch)
+    eng.optimizer_step(1.0)
+    captured(rec, eng, batch, 2, "frozen capture")
+    nb = args.batch - 5
+    phase(f"frozen sibling({nb})")
+    after = eng.sibling(nb)
+    phase("frozen sibling fused_step")
+    after.fused_step(*cut(batch, nb))
+    phase("frozen evaluate")
+    eng.pack()                                                   # (the sibling's step changed the weights)
+    eng.evaluate(*batch)
+    torch.cuda.synchronize()
+    bufs = engine_buffers(eng)
+    del eng, before, after
+
+    rec.hold()
+    phase("construct (modalities-only)")
+    eng, params, batch, _ = build(args)
+    rec.set_flat(eng)
+    phase("load_state_dict")
+    eng.load_state_dict(params)
+    phase("fused_step")
+    eng.fused_step(*batch)
+    phase("train_modalities_only")
+    eng.train_modalities_only()
+    for i in range(2):
+        phase(f"modal fused_step {i}")
+        eng.fused_step(*batch)
+    phase("probe")
+    eng.probe(*batch)
+    captured(rec, eng, batch, 1, "modal capture")
+    phase("modal evaluate")
+    eng.evaluate(*batch)
+    rec.hold()
+    phase("clone")
+    twin = eng.clone()
+    rec.set_flat(twin, "clone.", keep=True)
+    phase("clone fused_step")
+    twin.fused_step(*batch)
+    torch.cuda.synchronize()
+    bufs.update(engine_buffers(eng, "modal."))
+    bufs.update(engine_buffers(twin, "clone."))
+    return bufs
+
+
+def feed_buffers(eng, feed, tag=""):
+    """What a fed scenario adds to the hashed buffers: the training score table and ranking state, the feed's state, its
+    accumulators (`_acc`, as its two views: float64 sums, int64 counts) and its muting state."""
+    out = {}
+    if eng.scores is not None:
+        out[tag + "scores"] = eng.scores.table
+    if eng.rank is not None:
+        out[tag + "rank_state"] = eng.rank.state
+    out.update({tag + "feed_state": feed.state, tag + "feed_sums": feed.sums, tag + "feed_counts": feed.counts})
+    if feed.mute_state is not None:
+        out[tag + "feed_mute_state"] = feed.mute_state
+    return {k: t.detach().cpu() for k, t in out.items()}
+
+
+def scenario_feed(rec, args):
+    """Steps that feed themselves (EpochFeed, capture_feed) on an engine with count tables (and ranking buffers where the class
+    builds them), the ragged tail's sibling, evaluation into a split's table; then a muted feed on a frozen engine.  The tail's
+    training sibling is built before capture_feed, as sibling() demands, and takes its fed step after the replay."""
+    phase = lambda s: rec.emit("# " + s)
+    B, tail = args.batch, 5
+    n = 2 * B + tail                                             # two full batches and the ragged tail
+    ranks = args.model not in ("avmnist_uq", "mmimdb")           # (these two refuse rank_scores=True)
+    order = torch.randperm(n, generator=torch.Generator().manual_seed(args.seed + 3))
+    phase("construct")
+    eng, params, batch, rows = build(args, scores=True, rank_scores=ranks)
+    rec.set_flat(eng)
+    phase("load_state_dict")
+    eng.load_state_dict(params)
+    sources = rows(n, args.seed + 2)
+    phase("EpochFeed")
+    feed = E.EpochFeed(sources, B, eng.device)
+    phase(f"sibling({tail})")
+    tail_eng = eng.sibling(tail)
+    phase("capture_feed(steps=2)")
+    replay = eng.capture_feed(feed, steps=2)
+    phase("start(order)")
+    feed.start(order)
+    phase("replay")
+    replay()
+    phase("tail: fed step on the sibling")
+    tslots = feed.new_slots(tail)
+    tail_eng.pack()
+    feed.gather_into(tslots)
+    tail_eng.train_step(*tslots)
+    eng.pack()
+    feed.accumulate(tail_eng, tslots[-1])
+    phase("feed.read")
+    feed.read()
+    feed.check()
+    phase("evaluate into the tables of 'val'")
+    extra = {"rank": eng.rank_buffer("val")} if ranks else {}
+    eng.evaluate(*batch, scores=eng.score_table("val"), **extra)
+    torch.cuda.synchronize()
+    bufs = engine_buffers(eng)
+    bufs.update(feed_buffers(eng, feed))
+    bufs["scores_val"] = eng.score_table("val").table.cpu()
+    if ranks:
+        bufs["rank_val_state"] = eng.rank_buffer("val").state.cpu()
+    del eng, tail_eng, feed, replay
+
+    rec.hold()
+    phase("construct (frozen, muted feed)")
+    eng, params, batch, rows = build(args)
+    rec.set_flat(eng)
+    phase("load_state_dict")
+    eng.load_state_dict(params)
+    phase("freeze_modalities")
+    eng.freeze_modalities()
+    phase("EpochFeed(muting=True)")
+    feed = E.EpochFeed(sources, B, eng.device, muting=True)
+    phase("start(order, muting=codes)")
+    feed.start(order, muting=torch.tensor([1, 0, 2]))            # one code per step of the epoch: ceil(n / B) = 3
+    phase("capture_feed(steps=1)")
+    replay = eng.capture_feed(feed, steps=1)
+    for i in range(2):
+        phase(f"replay {i}")
+        replay()
+    torch.cuda.synchronize()
+    feed.check()
+    bufs.update(engine_buffers(eng, "muted."))
+    bufs.update(feed_buffers(eng, feed, "muted."))
+    return bufs
+
+
+SCENARIOS = {"base": scenario_base, "stages": scenario_stages, "feed": scenario_feed}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--model", required=True, help="avmnist_S | avmnist_M | avmnist_B | avmnist_uq | mmimdb | mimic")
+    ap.add_argument("--scenario", default="base", choices=sorted(SCENARIOS), help="the sequence of engine calls to trace")
+    ap.add_argument("--precision", default="bf16")
+    ap.add_argument("--batch", type=int, required=True)
+    ap.add_argument("--fusion", default=None, help="multimodal.fusion_function of a two-tower model")
+    ap.add_argument("--dropout", type=float, default=None)
+    ap.add_argument("--seed", type=int, default=11)
+    ap.add_argument("--out", default=None, help="file for the trace (default: stdout)")
+    ap.add_argument("--dump", default=None, help="also torch.save the hashed buffers here (for a max-abs-difference comparison)")
+    args = ap.parse_args()
+    out = open(args.out, "w") if args.out else sys.stdout
+    rec = Recorder(out)
+    rec.install()
+    bufs = SCENARIOS[args.scenario](rec, args)
+    rec.emit("# sha256")
     for k, t in bufs.items():
         out.write(f"sha256 {k} {hashlib.sha256(t.contiguous().numpy().tobytes()).hexdigest()}\n")
     out.flush()
