@@ -368,6 +368,29 @@ int m2m_heads_edl(const m2m_head* heads, int nheads, const int64_t* labels, int 
                   float* logits, float* losses, int32_t* preds, float* uncertainty, int32_t* combined,
                   int zero_losses, const float* weights, void* stream);
 
+/* m2m_heads_edl with a choice of Bayes risk and the annealed Dirichlet KL regulariser (additive within ABI 18; csrc/edl.hip):
+ * the pieces of modules/losses.py the reference's UQ model leaves unused.  Every argument up to `weights`, every output and the
+ * gradient contract are m2m_heads_edl's; m2m_heads_edl is this call with (M2M_EDL_MSE, NULL, NULL) and launches the same kernel.
+ *   risk     M2M_EDL_MSE: the squared-error risk above (EDLMSELoss, modules/losses.py:24-31);
+ *            M2M_EDL_CE:  L = psi(S) - psi(a_y) (EDLCELoss, modules/losses.py:71-93; :89-93 the risk),
+ *                         dL/dz_j = [z_j > 0] (psi1(S) - [j == y] psi1(a_j))
+ *   kl_coef  NULL: no KL term.  Else one device float, lambda, read by the launch (a captured graph follows it): the reference's
+ *            annealing coefficient min(1, epoch / annealing_step) (modules/losses.py:15-18, :81-84) times the caller's weight.
+ *            With at_k = a_k (k != y), at_y = 1, St = sum_k at_k (kl_divergence_loss, modules/losses.py:33-49 and :52-68):
+ *              KL = lgamma(St) - lgamma(K) - sum_k lgamma(at_k) + sum_k (at_k - 1)(psi(at_k) - psi(St))
+ *              dKL/dz_j = [z_j > 0][j != y] ((at_j - 1) psi1(at_j) - psi1(St)(St - K))
+ *              loss_h = mean_B(risk) + lambda mean_B(KL); dlogits carries coef_h / B, and lambda on its KL part.
+ *            lambda == 0.0f: the launch branches round all KL arithmetic -- the no-KL result bit for bit, kl_out not added to.
+ *   kl_out   NULL or nheads floats: kl_out[h] += the unscaled batch mean of KL (float atomics, one per workgroup; nothing at
+ *            lambda == 0); cleared together with `losses` when zero_losses is set.  Needs kl_coef.
+ * psi (digamma), psi1 (trigamma) and lgamma are fp32 device functions for arguments >= 1: the recurrence up to x >= 6, then the
+ * asymptotic series.  Refusals: m2m_heads_edl's, a risk other than the two, kl_out without kl_coef: -1, nothing launched. */
+#define M2M_EDL_MSE 0
+#define M2M_EDL_CE 1
+int m2m_heads_edl_risk(const m2m_head* heads, int nheads, const int64_t* labels, int B, int D, int K,
+                       float* logits, float* losses, int32_t* preds, float* uncertainty, int32_t* combined,
+                       int zero_losses, const float* weights, int risk, const float* kl_coef, float* kl_out, void* stream);
+
 /* m2m_towers_wgrad (above), which also adds the per-workgroup partial sums of the classification heads' weight gradients (m2m_head.g_part,
  * written by m2m_heads_ce at the same batch) to g_w / g_b: heads == NULL or nheads == 0: exactly m2m_towers_wgrad. */
 int m2m_towers_wgrad_heads(const m2m_tower* const* towers, const m2m_tower* const* dev_towers, int ntowers,
@@ -625,6 +648,11 @@ int m2m_feed_gather_muted(const m2m_feed_src* srcs, int nsrc, const int32_t* per
                           uint32_t* mute_state, void* stream);
 int m2m_epoch_accumulate(const float* losses, int nloss, const int32_t* preds, const int64_t* labels, int nheads, int B, double* sums,
                          uint64_t* counts, void* stream);
+/* The evidential model's epoch means (additive within ABI 18): models/avmnist.py:556-572 logs, per epoch, the mean over the steps of
+ * each step's batch-mean uncertainty (the ragged last batch counts as one step).  sums[h] += mean_r uncertainty[h][r] for
+ * h < nheads (uncertainty (nheads, B) fp32 as m2m_heads_edl writes it, sums float64): one value per step; the host divides by the
+ * step count of m2m_epoch_accumulate.  One workgroup, no atomics, a fixed summation order.  -1 on a NULL pointer, nheads < 1, B < 1. */
+int m2m_epoch_accumulate_uq(const float* uncertainty, int nheads, int B, double* sums, void* stream);
 
 /* ---- test hooks ----------------------------------------------------------------------------------- */
 /* keep-mask (uint8, 1 keep) the kernels use for dropout site `site` (0 tok hidden, 1 tok out,

@@ -100,6 +100,8 @@ SCORES_MAX_CLASSES, SCORES_MAX_LABELS = 64, 128    # m2m_scores_multiclass / _mu
 RANK_STATE_WORDS = 4                               # uint32 words of a ranking buffer's state (M2M_RANK_STATE_WORDS)
 FUSION_SUM, FUSION_MEAN, FUSION_MAX = 1, 2, 3     # m2m_fusion_forward / _backward modes (M2M_FUSION_*)
 FEED_MAX_SOURCES, FEED_STATE_WORDS = 4, 4          # m2m_feed_gather (M2M_FEED_MAX_SOURCES, M2M_FEED_STATE_WORDS)
+EDL_MSE, EDL_CE = 0, 1                             # m2m_heads_edl_risk's `risk` (M2M_EDL_MSE, M2M_EDL_CE)
+EDL_RISK_BY_NAME = {"mse": EDL_MSE, "ce": EDL_CE}
 FEED_MUTE_STATE_WORDS = 2                          # m2m_feed_gather_muted: step index, steps past the schedule
 
 
@@ -184,6 +186,9 @@ SIGNATURES = {
     "m2m_heads_bce_w": (C.c_int, [C.POINTER(Head), C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, C.c_int, _fp, _fp]),
     # evidential heads (csrc/edl.hip): m2m_heads_ce_w's arguments + uncertainty and combined behind preds
     "m2m_heads_edl": (C.c_int, [C.POINTER(Head), C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp, _fp]),
+    # ... + risk (EDL_MSE / EDL_CE), kl_coef (one device float or NULL) and kl_out (nheads floats or NULL) before the stream
+    "m2m_heads_edl_risk": (C.c_int, [C.POINTER(Head), C.c_int, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_int, _fp,
+                                     C.c_int, _fp, _fp, _fp]),
     # fusion functions other than ConcatFusion (csrc/fusion.hip)
     "m2m_fusion_forward": (C.c_int, [C.c_int, _fp, _fp, _fp, C.c_int64, _fp]),
     "m2m_fusion_backward": (C.c_int, [C.c_int, _fp, _fp, _fp, _fp, _fp, C.c_int64, _fp]),
@@ -201,6 +206,7 @@ SIGNATURES = {
     "m2m_feed_gather": (C.c_int, [C.POINTER(FeedSrc), C.c_int, _fp, C.c_int, _fp, _fp]),
     "m2m_feed_gather_muted": (C.c_int, [C.POINTER(FeedSrc), C.c_int, _fp, C.c_int, _fp, _fp, C.c_int, _fp, _fp]),
     "m2m_epoch_accumulate": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
+    "m2m_epoch_accumulate_uq": (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp]),
     "m2m_mlp_forward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, C.c_int, C.c_uint32, C.c_uint32,
                                   _fp, _fp]),
     "m2m_mlp_backward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, _fp]),

@@ -150,9 +150,15 @@ class EpochFeed:
       mute_codes  (ceil(n / B)) int32, one code per step of the epoch: 0 mutes nothing, s + 1 mutes source s (start writes them)
       mute_state  L.FEED_MUTE_STATE_WORDS uint32 (held as int32): the step index, steps that ran past the schedule
     and gather_into uses m2m_feed_gather_muted: the muted source's slot is filled with zero bytes, its rows are not read.
-    Both are allocated once: a captured graph keeps their pointers.  Off (the default): neither exists, nothing new is launched."""
+    Both are allocated once: a captured graph keeps their pointers.  Off (the default): neither exists, nothing new is launched.
 
-    def __init__(self, sources: Sequence[torch.Tensor], batch_size: int, device, muting: bool = False):
+    uncertainty=True (the evidential engine, AVMnistUQEngine): the feed also holds
+      unc_sums  (nheads of the engine's `uncertainty` buffer) float64: per step += the batch mean of each head's uncertainty
+    behind the counts in the same buffer (m2m_epoch_accumulate_uq, one more launch per step; models/avmnist.py:556-572 logs the
+    mean over steps of the step means, the ragged tail as one step).  Refused on an engine without an `uncertainty` buffer.  Off
+    (the default): a captured feed graph keeps exactly the nodes it had."""
+
+    def __init__(self, sources: Sequence[torch.Tensor], batch_size: int, device, muting: bool = False, uncertainty: bool = False):
         self.device = torch.device(device)
         self.sources = tuple(sources)
         self.B = int(batch_size)
@@ -178,6 +184,9 @@ class EpochFeed:
         self._acc: Optional[torch.Tensor] = None         # sums and counts in one 8-byte-cell buffer: one copy reads both
         self.nloss = self.nheads = None
         self.sums = self.counts = None
+        self.uncertainty = bool(uncertainty)
+        self.nunc = 0
+        self.unc_sums = None
 
     @staticmethod
     def _row_bytes(t: torch.Tensor) -> int:
@@ -187,13 +196,22 @@ class EpochFeed:
         """Size the accumulators for `engine`'s losses and heads (first use), or check that they fit it."""
         nloss = int(engine.losses.numel())
         nheads = int(engine.preds.shape[0]) if engine.preds.dim() == 2 else 0
+        nunc = 0
+        if self.uncertainty:
+            u = getattr(engine, "uncertainty", None)
+            if u is None:
+                raise RuntimeError(f"EpochFeed(uncertainty=True): {type(engine).__name__} has no `uncertainty` buffer (the "
+                                   "evidential engine, AVMnistUQEngine, has)")
+            nunc = int(u.shape[0])
         if self._acc is None:
-            self.nloss, self.nheads = nloss, nheads
-            self._acc = torch.zeros(2 * nloss + nheads + 2, dtype=torch.int64, device=self.device)
-            self.sums, self.counts = self._acc[:2 * nloss].view(torch.float64), self._acc[2 * nloss:]
-        elif (nloss, nheads) != (self.nloss, self.nheads):
-            raise RuntimeError(f"EpochFeed: accumulators sized for {self.nloss} losses / {self.nheads} heads, the engine has "
-                               f"{nloss} / {nheads}")
+            self.nloss, self.nheads, self.nunc = nloss, nheads, nunc
+            self._acc = torch.zeros(2 * nloss + nheads + 2 + nunc, dtype=torch.int64, device=self.device)
+            self.sums, self.counts = self._acc[:2 * nloss].view(torch.float64), self._acc[2 * nloss:2 * nloss + nheads + 2]
+            if nunc:
+                self.unc_sums = self._acc[2 * nloss + nheads + 2:].view(torch.float64)
+        elif (nloss, nheads, nunc) != (self.nloss, self.nheads, self.nunc):
+            raise RuntimeError(f"EpochFeed: accumulators sized for {self.nloss} losses / {self.nheads} heads / {self.nunc} "
+                               f"uncertainties, the engine has {nloss} / {nheads} / {nunc}")
 
     def new_slots(self, batch_size: Optional[int] = None) -> Tuple[torch.Tensor, ...]:
         """Zeroed input slots of one step: the sources' row shapes and dtypes at `batch_size` rows (default: the feed's)."""
@@ -258,12 +276,17 @@ class EpochFeed:
                 raise RuntimeError(f"EpochFeed: {int(ms[0])} gathers ran against a muting schedule of {int(self.mute_codes.numel())} "
                                    f"steps: {int(ms[1])} step(s) past its end muted nothing")
 
-    def read(self):
-        """(sums float64 (2 * nloss), counts int64 (nheads + 2)) on the host as numpy: one copy, the epoch's only synchronisation."""
+    def read(self, with_uncertainty: bool = False):
+        """(sums float64 (2 * nloss), counts int64 (nheads + 2)) on the host as numpy: one copy, the epoch's only synchronisation.
+        with_uncertainty (a feed built with uncertainty=True): a third array, unc_sums float64 (nunc), from the same copy."""
         if self._acc is None:
             raise RuntimeError("EpochFeed.read: no engine has used this feed yet")
+        if with_uncertainty and not self.nunc:
+            raise RuntimeError("EpochFeed.read: the uncertainty sums need a feed built with uncertainty=True")
         host = self._acc.cpu().numpy()
-        return host[:2 * self.nloss].view("float64").copy(), host[2 * self.nloss:].copy()
+        end = 2 * self.nloss + self.nheads + 2
+        out = (host[:2 * self.nloss].view("float64").copy(), host[2 * self.nloss:end].copy())
+        return out + (host[end:].view("float64").copy(),) if with_uncertainty else out
 
     def gather_into(self, slots: Sequence[torch.Tensor]):
         """Enqueue the gather of the next slots[0].shape[0] rows of the order into `slots` (one per source, as new_slots makes
@@ -295,3 +318,9 @@ class EpochFeed:
         L.check(L.lib().m2m_epoch_accumulate(engine.losses.data_ptr(), self.nloss, L.ptr(preds), L.ptr(labels) if self.nheads else 0,
                                              self.nheads, engine.B, self.sums.data_ptr(), self.counts.data_ptr(), L.stream_ptr()),
                 "epoch_accumulate")
+        if self.nunc:
+            u = engine.uncertainty
+            if tuple(u.shape) != (self.nunc, engine.B) or u.dtype != torch.float32 or not u.is_contiguous():
+                raise RuntimeError(f"EpochFeed.accumulate: uncertainty must be contiguous float32 ({self.nunc}, {engine.B})")
+            L.check(L.lib().m2m_epoch_accumulate_uq(u.data_ptr(), self.nunc, engine.B, self.unc_sums.data_ptr(), L.stream_ptr()),
+                    "epoch_accumulate_uq")

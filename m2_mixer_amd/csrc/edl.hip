@@ -10,7 +10,7 @@
 //     u_h = K / S                                                                                   (avmnist.py:525-531)
 //     combined = preds_h of the head whose u_h is strictly below every other head's, else 0         (avmnist.py:533-537)
 // The reference multiplies its KL term by annealing_coef * 0 (losses.py:20): it adds nothing to the value or the gradient and the
-// epoch number has no effect, so it is left out here.
+// epoch number has no effect, so m2m_heads_edl leaves it out (m2m_heads_edl_risk, below, has it as an option).
 // Gradient (closed form; sums over k):
 //     dz_j = [z_j > 0] (dE_j + dV_j) coef_h / B
 //     dE_j = (-2 / S) [(y_j - p_j) - sum_k (y_k - p_k) p_k]
@@ -19,6 +19,19 @@
 // Everything is fp32.  The phases around the loss -- pooled rows and weights into LDS, logits, d_pooled, g_w / g_b or the g_part
 // slots -- are those of heads.hip's cross-entropy kernel on the same grid (m2m_heads_part_tiles(B) sample tiles x heads), so the
 // unchanged m2m_towers_wgrad_heads adds the slots.
+//
+// m2m_heads_edl_risk adds the two pieces of modules/losses.py the reference's UQ model does not train with -- the cross-entropy
+// Bayes risk (EDLCELoss, modules/losses.py:71-93) and the Dirichlet KL regulariser (modules/losses.py:33-49 and :52-68, the same
+// function twice) under an annealed coefficient lambda (:15-18, :81-84: min(1, epoch / annealing_step), times the caller's weight):
+//     CE risk   L = psi(S) - psi(a_y)                          dL/dz_j = [z_j > 0] (psi1(S) - [j == y] psi1(a_j))       (:89-93)
+//     KL        at_k = a_k (k != y), at_y = 1, St = sum_k at_k = S - a_y + 1                                            (:52-68)
+//               KL = lgamma(St) - lgamma(K) - sum_k lgamma(at_k) + sum_k (at_k - 1)(psi(at_k) - psi(St))
+//               dKL/dz_j = [z_j > 0][j != y] ((at_j - 1) psi1(at_j) - psi1(St)(St - K))
+//     loss_h = mean_B(risk) + lambda mean_B(KL);  dlogits carries coef_h / B, and lambda on the KL part
+// psi = digamma, psi1 = trigamma: fp32 device functions below, for arguments >= 1 only (a >= 1, S >= K, St >= K).  The risk and
+// the presence of the KL term are template parameters: <MSE, no KL> is the kernel m2m_heads_edl always launched.  lambda is one
+// device float (a captured graph follows it); lambda == 0 takes a workgroup-uniform branch round all KL arithmetic, so that form
+// costs nothing, equals the no-KL result bit for bit, and an overflowing lgamma never meets a zero factor.
 #include "dispatch.h"
 
 #define EDL_S 16        // samples per workgroup (4 at B <= 64): the grid of heads.hip
@@ -28,9 +41,58 @@
 struct EdlArgs {
     m2m_head h[EDL_MAXH];
     const float* weights;       // nheads device floats read in place of m2m_head.weight, or NULL
+    const float* kl_coef;       // (KL instantiations) one device float: lambda
+    float* kl_out;              // (KL instantiations) nheads floats += the unscaled batch-mean KL, or NULL
+    float lgamma_k;             // lgamma(K), from the host
 };
 
-template <int S, int DD>
+// ---- digamma, trigamma and lgamma for x >= 1: the recurrence up to x >= 6 (five steps at the most, taken without a branch), then
+// ---- the asymptotic series, whose first dropped term is below 3e-9 of the value at x = 6 ------------------------------------------
+// psi(x) = psi(x + 1) - 1 / x;  psi(x) ~ ln x - 1/(2x) - 1/(12 x^2) + 1/(120 x^4) - 1/(252 x^6) + 1/(240 x^8)
+static __device__ __forceinline__ float edl_digamma(float x) {
+    float r = 0.f;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const bool low = x < 6.f;
+        r -= low ? 1.f / x : 0.f;
+        x += low ? 1.f : 0.f;
+    }
+    const float ix = 1.f / x, ix2 = ix * ix;
+    const float series = ix2 * (1.f / 12.f - ix2 * (1.f / 120.f - ix2 * (1.f / 252.f - ix2 * (1.f / 240.f))));
+    return r + (logf(x) - 0.5f * ix - series);
+}
+
+// psi1(x) = psi1(x + 1) + 1 / x^2;  psi1(x) ~ 1/x + 1/(2 x^2) + 1/(6 x^3) - 1/(30 x^5) + 1/(42 x^7) - 1/(30 x^9)
+static __device__ __forceinline__ float edl_trigamma(float x) {
+    float r = 0.f;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const bool low = x < 6.f;
+        const float ix = 1.f / x;
+        r += low ? ix * ix : 0.f;
+        x += low ? 1.f : 0.f;
+    }
+    const float ix = 1.f / x, ix2 = ix * ix;
+    const float series = ix * (1.f + ix * (0.5f + ix * (1.f / 6.f - ix2 * (1.f / 30.f - ix2 * (1.f / 42.f - ix2 * (1.f / 30.f))))));
+    return r + series;
+}
+
+// lgamma(x) = lgamma(x + n) - ln(x (x + 1) ... (x + n - 1))  (the product stays below 6^5);
+// lgamma(x) ~ (x - 1/2) ln x - x + ln(2 pi) / 2 + 1/(12 x) - 1/(360 x^3) + 1/(1260 x^5)
+static __device__ __forceinline__ float edl_lgamma(float x) {
+    float prod = 1.f;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const bool low = x < 6.f;
+        prod *= low ? x : 1.f;
+        x += low ? 1.f : 0.f;
+    }
+    const float ix = 1.f / x, ix2 = ix * ix;
+    const float series = ix * (1.f / 12.f - ix2 * (1.f / 360.f - ix2 * (1.f / 1260.f)));
+    return ((x - 0.5f) * logf(x) - x + 0.91893853320467274f + series) - logf(prod);
+}
+
+template <int S, int DD, int RISK, bool KL>
 __global__ __launch_bounds__(NTHREADS) void heads_edl_kernel(const EdlArgs ha, const int64_t* __restrict__ labels, int B, int K,
                                                              float* __restrict__ logits_out, float* __restrict__ losses,
                                                              int32_t* __restrict__ preds, float* __restrict__ uncertainty,
@@ -41,6 +103,7 @@ __global__ __launch_bounds__(NTHREADS) void heads_edl_kernel(const EdlArgs ha, c
     float* wl = pl + S * DL;                              // weights     [EDL_MAXK][DL]
     float* lg = wl + EDL_MAXK * DL;                       // logits / dlogits [S][EDL_MAXK]
     float* red = lg + S * EDL_MAXK;                       // [S] loss terms
+    float* klr = red + S;                                 // [S] KL terms (KL instantiations only: the others have no such array)
 
     const int tid = threadIdx.x;
     const int hI = blockIdx.y;
@@ -133,20 +196,50 @@ __global__ __launch_bounds__(NTHREADS) void heads_edl_kernel(const EdlArgs ha, c
             st += __shfl_xor(st, o, 64);
         }
         const int y = sI < ns ? (int)labels[s0 + sI] : 0;
-        const float p = al / st;
-        const float d = live ? (k == y ? 1.f : 0.f) - p : 0.f;
-        const float s1 = st + 1.f;
-        float term = d * d + p * (1.f - p) / s1;              // dead lanes: p = d = 0
-        float sdp = d * p, sp2 = p * p;
+        float term, dl;
+        if constexpr (RISK == M2M_EDL_MSE) {
+            const float p = al / st;
+            const float d = live ? (k == y ? 1.f : 0.f) - p : 0.f;
+            const float s1 = st + 1.f;
+            term = d * d + p * (1.f - p) / s1;                // dead lanes: p = d = 0
+            float sdp = d * p, sp2 = p * p;
 #pragma unroll
-        for (int o = 16; o >= 1; o >>= 1) {
-            term += __shfl_xor(term, o, 64);
-            sdp += __shfl_xor(sdp, o, 64);
-            sp2 += __shfl_xor(sp2, o, 64);
+            for (int o = 16; o >= 1; o >>= 1) {
+                term += __shfl_xor(term, o, 64);
+                sdp += __shfl_xor(sdp, o, 64);
+                sp2 += __shfl_xor(sp2, o, 64);
+            }
+            const float dE = (-2.f / st) * (d - sdp);
+            const float dV = ((-2.f / st) / s1) * (p - sp2) - ((1.f - sp2) / s1) / s1;
+            dl = (sI < ns && z > 0.f) ? (hw / (float)B) * (dE + dV) : 0.f;
+        } else {
+            // lane k evaluates its own class: psi(a_k) is read on the label's lane only, psi1(S) is the same on all 32
+            const bool hit = live && k == y;
+            const float ak = live ? al : 1.f;
+            term = hit ? edl_digamma(st) - edl_digamma(ak) : 0.f;
+#pragma unroll
+            for (int o = 16; o >= 1; o >>= 1) term += __shfl_xor(term, o, 64);
+            const float g = edl_trigamma(st) - (hit ? edl_trigamma(ak) : 0.f);
+            dl = (sI < ns && z > 0.f) ? (hw / (float)B) * g : 0.f;
         }
-        const float dE = (-2.f / st) * (d - sdp);
-        const float dV = ((-2.f / st) / s1) * (p - sp2) - ((1.f - sp2) / s1) / s1;
-        const float dl = (sI < ns && z > 0.f) ? (hw / (float)B) * (dE + dV) : 0.f;
+        if constexpr (KL) {
+            const float lam = *ha.kl_coef;                    // one uniform load; the branch is the same for the whole grid
+            if (lam != 0.f) {
+                const bool other = live && k != y;            // the label's lane has at = 1: lgamma(1) = 0, at - 1 = 0
+                const float at = other ? al : 1.f;
+                float stt = live ? at : 0.f;                  // St = sum_k at_k
+#pragma unroll
+                for (int o = 16; o >= 1; o >>= 1) stt += __shfl_xor(stt, o, 64);
+                const float psit = edl_digamma(stt);
+                float kl = other ? (at - 1.f) * (edl_digamma(at) - psit) - edl_lgamma(at) : 0.f;
+#pragma unroll
+                for (int o = 16; o >= 1; o >>= 1) kl += __shfl_xor(kl, o, 64);
+                kl += edl_lgamma(stt) - ha.lgamma_k;
+                const float gk = (at - 1.f) * edl_trigamma(at) - edl_trigamma(stt) * (stt - (float)K);
+                if (sI < ns && z > 0.f && other) dl += (hw / (float)B) * (lam * gk);
+                if (k == 0) klr[sI] = sI < ns ? kl : 0.f;
+            }
+        }
         if (live) lg[sI * EDL_MAXK + k] = dl;
         if (k == 0) {
             red[sI] = sI < ns ? term : 0.f;
@@ -162,6 +255,17 @@ __global__ __launch_bounds__(NTHREADS) void heads_edl_kernel(const EdlArgs ha, c
 #pragma unroll
         for (int sI = 0; sI < S; ++sI) t += red[sI];
         t /= (float)B;
+        if constexpr (KL) {
+            const float lam = *ha.kl_coef;
+            if (lam != 0.f) {                                 // (the loss phase's branch: klr was written)
+                float tk = 0.f;
+#pragma unroll
+                for (int sI = 0; sI < S; ++sI) tk += klr[sI];
+                tk /= (float)B;
+                t += lam * tk;
+                if (ha.kl_out) atomicAdd(ha.kl_out + hI, tk);
+            }
+        }
         atomicAdd(losses + hI, t);
         atomicAdd(losses + nheads, t * hw);
     }
@@ -227,24 +331,40 @@ __global__ void edl_combine_kernel(const int32_t* preds, const float* __restrict
 }
 
 // (the losses are cleared by a kernel, as in heads.hip: a small memset node misbehaved on hipGraph replay)
-__global__ void edl_zero_floats_kernel(float* p, int n) {
+__global__ void edl_zero_floats_kernel(float* p, int n, float* q, int nq) {
     if ((int)threadIdx.x < n) p[threadIdx.x] = 0.f;
+    if ((int)threadIdx.x < nq) q[threadIdx.x] = 0.f;         // (kl_out, cleared together with the losses)
 }
 
-template <int S>
+template <int S, int RISK, bool KL>
 static int launch_edl_s(const EdlArgs& ha, int nheads, const int64_t* labels, int B, int D, int K, float* logits, float* losses,
                         int32_t* preds, float* uncertainty, hipStream_t st) {
     return m2m_dispatch(m2m_wide_dims{}, D, M2M_NO_BUILD, [&](auto DD) {
         constexpr int Dc = decltype(DD)::value;
-        const size_t lds = sizeof(float) * ((size_t)S * (Dc + 4) + (size_t)EDL_MAXK * (Dc + 4) + S * EDL_MAXK + S);
-        return m2m_launch<heads_edl_kernel<S, Dc>>(dim3((B + S - 1) / S, nheads), dim3(NTHREADS), lds, 160 * 1024, st, ha, labels, B, K,
-                                                   logits, losses, preds, uncertainty, nheads);
+        const size_t lds = sizeof(float) * ((size_t)S * (Dc + 4) + (size_t)EDL_MAXK * (Dc + 4) + S * EDL_MAXK + S + (KL ? S : 0));
+        return m2m_launch<heads_edl_kernel<S, Dc, RISK, KL>>(dim3((B + S - 1) / S, nheads), dim3(NTHREADS), lds, 160 * 1024, st, ha, labels,
+                                                             B, K, logits, losses, preds, uncertainty, nheads);
     });
 }
 
-extern "C" int m2m_heads_edl(const m2m_head* heads, int nheads, const int64_t* labels, int B, int D, int K, float* logits,
-                             float* losses, int32_t* preds, float* uncertainty, int32_t* combined, int zero_losses,
-                             const float* weights, void* stream) {
+template <int RISK, bool KL>
+static int launch_edl(int S, const EdlArgs& ha, int nheads, const int64_t* labels, int B, int D, int K, float* logits, float* losses,
+                      int32_t* preds, float* uncertainty, hipStream_t st) {
+    return S == 4 ? launch_edl_s<4, RISK, KL>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st)
+                  : launch_edl_s<EDL_S, RISK, KL>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st);
+}
+
+extern "C" int m2m_heads_edl_risk(const m2m_head* heads, int nheads, const int64_t* labels, int B, int D, int K, float* logits,
+                                  float* losses, int32_t* preds, float* uncertainty, int32_t* combined, int zero_losses,
+                                  const float* weights, int risk, const float* kl_coef, float* kl_out, void* stream) {
+    if (risk != M2M_EDL_MSE && risk != M2M_EDL_CE) {
+        m2m_set_error("heads_edl: risk must be M2M_EDL_MSE (0) or M2M_EDL_CE (1)", __FILE__, __LINE__);
+        return -1;
+    }
+    if (kl_out && !kl_coef) {
+        m2m_set_error("heads_edl: kl_out needs kl_coef (without the KL term there is nothing to report)", __FILE__, __LINE__);
+        return -1;
+    }
     if (!heads || nheads < 1 || nheads > EDL_MAXH || K < 2 || K > EDL_MAXK || B < 1) {
         m2m_set_error("heads_edl: unsupported (1..4 heads, K in 2..32, B >= 1)", __FILE__, __LINE__);
         return -1;
@@ -280,14 +400,30 @@ extern "C" int m2m_heads_edl(const m2m_head* heads, int nheads, const int64_t* l
         }
     }
     ha.weights = weights;
+    ha.kl_coef = kl_coef;
+    ha.kl_out = kl_out;
+    ha.lgamma_k = (float)lgamma((double)K);
     for (int i = 0; i < nheads; ++i) ha.h[i] = heads[i];
     for (int i = nheads; i < EDL_MAXH; ++i) ha.h[i] = heads[0];
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (zero_losses) hipLaunchKernelGGL(edl_zero_floats_kernel, dim3(1), dim3(64), 0, st, losses, nheads + 1);
-    const int rc = S == 4 ? launch_edl_s<4>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st)
-                          : launch_edl_s<EDL_S>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st);
+    if (zero_losses) hipLaunchKernelGGL(edl_zero_floats_kernel, dim3(1), dim3(64), 0, st, losses, nheads + 1, kl_out, kl_out ? nheads : 0);
+    int rc;
+    if (risk == M2M_EDL_MSE) {
+        rc = kl_coef ? launch_edl<M2M_EDL_MSE, true>(S, ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st)
+                     : launch_edl<M2M_EDL_MSE, false>(S, ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st);
+    } else {
+        rc = kl_coef ? launch_edl<M2M_EDL_CE, true>(S, ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st)
+                     : launch_edl<M2M_EDL_CE, false>(S, ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st);
+    }
     if (rc != 0) return rc;
     hipLaunchKernelGGL(edl_combine_kernel, dim3((B + 255) / 256), dim3(256), 0, st, preds, uncertainty, combined, B, nheads);
     M2M_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+extern "C" int m2m_heads_edl(const m2m_head* heads, int nheads, const int64_t* labels, int B, int D, int K, float* logits,
+                             float* losses, int32_t* preds, float* uncertainty, int32_t* combined, int zero_losses,
+                             const float* weights, void* stream) {
+    return m2m_heads_edl_risk(heads, nheads, labels, B, D, K, logits, losses, preds, uncertainty, combined, zero_losses, weights,
+                              M2M_EDL_MSE, nullptr, nullptr, stream);
 }

@@ -190,6 +190,20 @@ __global__ __launch_bounds__(64) void epoch_accumulate_kernel(const float* __res
     }
 }
 
+// The evidential model's epoch means (models/avmnist.py:556-572 logs the mean over steps of the step's batch-mean uncertainty):
+// sums[h] += mean_r uncertainty[h][r], one value per step.  One wavefront, no atomics; the batch sum is taken in float64, lanes
+// striding the rows, then a butterfly: the same order on every call.
+__global__ __launch_bounds__(64) void epoch_accumulate_uq_kernel(const float* __restrict__ uncertainty, int nheads, int B, double* sums) {
+    const int lane = threadIdx.x;
+    for (int h = 0; h < nheads; ++h) {
+        double s = 0.0;
+        for (int r = lane; r < B; r += 64) s += (double)uncertainty[(int64_t)h * B + r];
+#pragma unroll
+        for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o, 64);
+        if (lane == 0) sums[h] += s / (double)B;
+    }
+}
+
 // The checks and the tile list both gathers share; -1 (m2m_last_error) before anything is launched.
 static int feed_build_args(const m2m_feed_src* srcs, int nsrc, int B, const uint32_t* state, FeedArgs& a) {
     if (!srcs || !state) {
@@ -297,6 +311,20 @@ extern "C" int m2m_epoch_accumulate(const float* losses, int nloss, const int32_
     }
     hipLaunchKernelGGL(epoch_accumulate_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), losses, nloss, preds, labels,
                        nheads, B, sums, reinterpret_cast<unsigned long long*>(counts));
+    M2M_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+extern "C" int m2m_epoch_accumulate_uq(const float* uncertainty, int nheads, int B, double* sums, void* stream) {
+    if (!uncertainty || !sums) {
+        m2m_set_error("epoch_accumulate_uq: uncertainty and sums must be given (no NULL pointers)", __FILE__, __LINE__);
+        return -1;
+    }
+    if (nheads < 1 || B < 1) {
+        m2m_set_error("epoch_accumulate_uq: needs nheads >= 1 and B >= 1", __FILE__, __LINE__);
+        return -1;
+    }
+    hipLaunchKernelGGL(epoch_accumulate_uq_kernel, dim3(1), dim3(64), 0, reinterpret_cast<hipStream_t>(stream), uncertainty, nheads, B, sums);
     M2M_CHECK_HIP(hipGetLastError());
     return 0;
 }

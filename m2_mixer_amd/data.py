@@ -271,7 +271,9 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
 
     Returns run_epoch's keys from feed.read(): loss, loss_step_mean, the per-head losses, steps, samples and -- for engines whose
     predictions are classes -- acc*, hits*; the score table's and ranking buffer's numbers (scores=True / rank_scores=True) are
-    merged in as run_epoch does, under the table of `split`.  Ends with feed.check(): a pass that ran beyond the order raises."""
+    merged in as run_epoch does, under the table of `split`.  A feed built with uncertainty=True (the evidential engine) adds
+    uncertainty, uncertainty_<a>, uncertainty_<b>: the epoch means of the steps' batch-mean uncertainties.  Ends with feed.check():
+    a pass that ran beyond the order raises."""
     n = feed.n if n is None else int(n)
     B = feed.B
     if not 0 <= n <= feed.n:
@@ -332,7 +334,11 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
         else:
             tail_engine.evaluate(*tslots, **extra)
         feed.accumulate(tail_engine, tslots[-1])
-    sums, counts = feed.read()                                     # the only sync of the epoch
+    unc = None
+    if feed.nunc:
+        sums, counts, unc = feed.read(with_uncertainty=True)       # the only sync of the epoch
+    else:
+        sums, counts = feed.read()
     feed.check()
     nl, nh = feed.nloss, feed.nheads
     nsteps, seen = int(counts[nh]), int(counts[nh + 1])
@@ -347,4 +353,8 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
     if nh == 3:
         out.update({"acc": int(counts[2]) / dn, f"acc_{a}": int(counts[0]) / dn, f"acc_{b}": int(counts[1]) / dn,
                     "hits": int(counts[2]), f"hits_{a}": int(counts[0]), f"hits_{b}": int(counts[1])})
+    if unc is not None:
+        # the mean over the steps of each step's batch mean, the ragged tail as one step (models/avmnist.py:556-572); rows are
+        # the engine's [a, b, fusion], the plain name is the fusion head's
+        out.update({"uncertainty": float(unc[2]) / ds, f"uncertainty_{a}": float(unc[0]) / ds, f"uncertainty_{b}": float(unc[1]) / ds})
     return out

@@ -1397,7 +1397,21 @@ class AVMnistUQEngine(AVMnistEngine):
         argmax is not kept; it is argmax relu(logits[2]));
       * `uncertainty` (3, B) fp32 rows are [image, audio, fusion]; evaluate() returns them too.  A multi-step captured graph
         (capture(steps > 1)) writes every step's values there: afterwards it holds the last step's;
-      * rank_scores=True is refused: the ranking buffers store a softmax, which is not this model's class probability."""
+      * rank_scores=True is refused: the ranking buffers store a softmax, which is not this model's class probability.
+
+    Three cfg keys choose the loss among the pieces of the reference's modules/losses.py (the reference hard-codes them; the keys
+    are this build's extension).  The defaults are the reference's model, and with them nothing differs from an engine without
+    the keys: m2m_heads_edl is called, no further buffer exists.
+      * `edl_loss`: "mse" (default; EDLMSELoss, losses.py:24-31) or "ce" (EDLCELoss, :71-93): the Bayes risk of every head;
+      * `kl_weight` (default 0.0) > 0 adds lambda x the Dirichlet KL regulariser (kl_divergence_loss, :52-68) to every head's loss,
+        lambda = kl_weight x min(1, epoch / annealing_step) (:15-18);
+      * `annealing_step` (default 10: the reference's EDLMSELoss(num_classes, 10)).
+    With kl_weight > 0 the engine owns `kl_coef`, one device float holding lambda (shared with siblings like `loss_weights`; a
+    clone gets a copy), and `kl` (3,): the heads' unscaled batch-mean KL of the last pass.  set_epoch(epoch) writes lambda in
+    place: captured graphs and feed graphs follow from their next replay.  Evaluation uses the same lambda (the reference passes
+    current_epoch in validation too).  A new engine is at epoch 0: lambda = 0, where the launch skips all KL arithmetic."""
+
+    EDL_LOSSES = ("mse", "ce")
 
     def __init__(self, cfg: dict, batch_size: int, device="cuda:0", precision: Optional[str] = None,
                  lr: float = 1e-2, betas=(0.9, 0.999), eps: float = 1e-8, weight_decay: float = 0.0,
@@ -1406,20 +1420,62 @@ class AVMnistUQEngine(AVMnistEngine):
         if rank_scores:
             raise RuntimeError("AVMnistUQEngine: rank_scores=True: the ranking buffers store the softmax of the logits, which is "
                                "not the evidential model's class probability (alpha / S)")
+        self.edl_loss = cfg.get("edl_loss", "mse")
+        self.kl_weight = float(cfg.get("kl_weight", 0.0))
+        self.annealing_step = cfg.get("annealing_step", 10)
+        if self.edl_loss not in self.EDL_LOSSES:
+            raise ValueError(f"AVMnistUQEngine: edl_loss must be one of {', '.join(self.EDL_LOSSES)}, got {self.edl_loss!r}")
+        if not self.kl_weight >= 0.0 or not self.annealing_step > 0:
+            raise ValueError("AVMnistUQEngine: kl_weight >= 0 and annealing_step > 0")
         self.head_weights = {"image": 1.0, "audio": 1.0, "fusion": 1.0}
         # (past AVMnistEngine.__init__, which derives the coefficients from a fusion_loss_weight this model does not have)
         _TwoTowerEngine.__init__(self, cfg, batch_size, device, precision, lr, betas, eps, weight_decay, seed, init, share, scores,
                                  rank_scores, rank_capacity)
         self.uncertainty = torch.zeros(3, self.B, device=self.device)
+        # the epoch the family is at (host side) and, with the KL term, lambda on the device: shared like loss_weights
+        self._epoch_group = share._epoch_group if share is not None else {"epoch": 0}
+        self.kl_coef = self.kl = None
+        if self.kl_weight > 0.0:
+            self.kl_coef = share.kl_coef if share is not None else torch.zeros(1, device=self.device)
+            self.kl = torch.zeros(3, device=self.device)
 
     def set_fusion_loss_weight(self, w: float):
         raise NotImplementedError("AVMnistUQEngine: its loss has no fusion_loss_weight (models/avmnist.py:511)")
 
+    @property
+    def epoch(self) -> int:
+        return self._epoch_group["epoch"]
+
+    def kl_lambda(self, epoch: Optional[int] = None) -> float:
+        """kl_weight x min(1, epoch / annealing_step) (modules/losses.py:15-18) at `epoch` (default: the engine's)."""
+        e = self.epoch if epoch is None else epoch
+        return self.kl_weight * min(1.0, e / self.annealing_step)
+
+    def set_epoch(self, epoch: int):
+        """The epoch the KL term's annealing coefficient follows: lambda is written in place into `kl_coef`, on the current stream
+        (behind the steps already enqueued there) -- this engine, its siblings and every graph captured from them read the new
+        value from their next launch on; no capture is dropped.  Without the KL term (kl_weight == 0) only the number is kept."""
+        if epoch < 0:
+            raise ValueError("set_epoch: epoch >= 0")
+        self._epoch_group["epoch"] = epoch
+        if self.kl_coef is not None:
+            self.kl_coef.fill_(self.kl_lambda())
+
+    def clone(self, batch_size: Optional[int] = None):
+        new = super().clone(batch_size)
+        new.set_epoch(self.epoch)                             # (its own table and epoch, at this engine's values)
+        return new
+
     def _loss_heads(self, heads, labels, zero_losses):
         # (self.preds at call time: a multi-step capture points it at its per-step slots)
-        heads_edl(heads, labels, self.B, self.D, self.K,
-                  out=(self.logits, self.losses, self.preds, self.uncertainty, self.preds[2]), zero_losses=zero_losses,
-                  weights=self._step_weights)
+        out = (self.logits, self.losses, self.preds, self.uncertainty, self.preds[2])
+        if self.edl_loss == "mse" and self.kl_coef is None:
+            heads_edl(heads, labels, self.B, self.D, self.K, out=out, zero_losses=zero_losses, weights=self._step_weights)
+            return
+        if self.kl is not None and not zero_losses:
+            self.kl.zero_()                                   # (a training step's prologue cleared the losses, not this)
+        heads_edl(heads, labels, self.B, self.D, self.K, out=out, zero_losses=zero_losses, weights=self._step_weights,
+                  risk=self.edl_loss, kl_coef=self.kl_coef, kl_out=self.kl)
 
     def _heads_are_ce(self) -> bool:
         return False                                          # no fused heads + fusion-backward launch: that one computes cross-entropy

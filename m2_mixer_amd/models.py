@@ -661,16 +661,62 @@ def edl_mse_loss(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
     return ((target - p) ** 2 + p * (1 - p) / (strength + 1)).sum(dim=-1).mean()
 
 
-class EDLMSELoss(nn.Module):
-    """The reference's criterion module (modules/losses.py:5-31) around edl_mse_loss: no parameters, no buffers; `epoch_num` is
-    accepted and has no effect (the KL term it would anneal is times 0)."""
+def edl_ce_loss(logits: torch.Tensor, labels: torch.Tensor) -> torch.Tensor:
+    """The cross-entropy Bayes risk of the reference's EDLCELoss (modules/losses.py:89-93): psi(S) - psi(alpha_y), batch mean."""
+    alpha = torch.relu(logits) + 1.0
+    alpha_y = alpha.gather(-1, labels.unsqueeze(-1)).squeeze(-1)
+    return (torch.digamma(alpha.sum(dim=-1)) - torch.digamma(alpha_y)).mean()
 
-    def __init__(self, num_classes: int, annealing_step: int = 10):
+
+def kl_divergence_loss(evidence: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """The reference's kl_divergence_loss (modules/losses.py:52-68; :33-49 is the same function as a method): KL(Dir(at) || Dir(1))
+    with the label's evidence removed -- at = alpha off the label, 1 on it -- batch mean.  evidence (B, K) >= 0, target one-hot."""
+    at = target + (1 - target) * (evidence + 1.0)
+    st = at.sum(dim=-1)
+    k = at.new_tensor(float(evidence.shape[-1]))
+    log_norm = torch.lgamma(st) - torch.lgamma(k) - torch.lgamma(at).sum(dim=-1)
+    spread = ((at - 1) * (torch.digamma(at) - torch.digamma(st).unsqueeze(-1))).sum(dim=-1)
+    return (log_norm + spread).mean()
+
+
+def annealing_coef(epoch_num, annealing_step) -> torch.Tensor:
+    """min(1, epoch_num / annealing_step) as the reference takes it: float32 (modules/losses.py:15-18, :81-84)."""
+    return torch.min(torch.tensor(1.0, dtype=torch.float32), torch.tensor(epoch_num / annealing_step, dtype=torch.float32))
+
+
+class _EDLLoss(nn.Module):
+    """A Bayes risk + kl_weight x annealing_coef(epoch_num) x kl_divergence_loss: no parameters, no buffers.  kl_weight = 0 (the
+    default, what the reference's models train with) adds nothing, not even a zero."""
+
+    risk = None
+
+    def __init__(self, num_classes: int, annealing_step: int = 10, kl_weight: float = 0.0):
         super().__init__()
-        self.num_classes, self.annealing_step = num_classes, annealing_step
+        self.num_classes, self.annealing_step, self.kl_weight = num_classes, annealing_step, float(kl_weight)
 
     def forward(self, output, y, epoch_num: int = 0):
-        return edl_mse_loss(output, y)
+        loss = type(self).risk(output, y)
+        if self.kl_weight == 0.0:
+            return loss
+        target = torch.nn.functional.one_hot(y, output.shape[-1]).to(output.dtype)
+        lam = self.kl_weight * annealing_coef(epoch_num, self.annealing_step).to(output.device)
+        return loss + lam * kl_divergence_loss(torch.relu(output), target)
+
+
+class EDLMSELoss(_EDLLoss):
+    """The reference's criterion module (modules/losses.py:5-31) around edl_mse_loss.  With the default kl_weight = 0 `epoch_num`
+    is accepted and has no effect (the reference's KL term is times 0); kl_weight > 0 is this build's extension."""
+
+    risk = staticmethod(edl_mse_loss)
+
+
+class EDLCELoss(_EDLLoss):
+    """The reference's EDLCELoss (modules/losses.py:71-93) around edl_ce_loss, with the same optional KL term."""
+
+    risk = staticmethod(edl_ce_loss)
+
+
+EDL_LOSSES = {"mse": EDLMSELoss, "ce": EDLCELoss}
 
 
 class AVMnistMixerMultiLossUQ(AVMnistMixerMultiLoss):
@@ -686,9 +732,15 @@ class AVMnistMixerMultiLossUQ(AVMnistMixerMultiLoss):
     def __init__(self, model_cfg, optimizer_cfg, **kwargs):
         super().__init__(model_cfg, optimizer_cfg, **kwargs)
         self.num_classes = self.model_cfg.modalities.classification.num_classes
-        self.image_criterion = EDLMSELoss(self.num_classes, 10)                                   # models/avmnist.py:451-453
-        self.audio_criterion = EDLMSELoss(self.num_classes, 10)
-        self.fusion_criterion = EDLMSELoss(self.num_classes, 10)
+        # models/avmnist.py:451-453 hard-codes EDLMSELoss(num_classes, 10); the three keys are this build's extension
+        self.edl_loss = self.model_cfg.get("edl_loss", "mse")
+        self.kl_weight = float(self.model_cfg.get("kl_weight", 0.0))
+        self.annealing_step = self.model_cfg.get("annealing_step", 10)
+        if self.edl_loss not in EDL_LOSSES:
+            raise ValueError(f"edl_loss must be one of {', '.join(EDL_LOSSES)}, got {self.edl_loss!r}")
+        make = lambda: EDL_LOSSES[self.edl_loss](self.num_classes, self.annealing_step, self.kl_weight)
+        self.image_criterion, self.audio_criterion, self.fusion_criterion = make(), make(), make()
+        self._engine_epoch = None                    # the epoch the bound engine's lambda was last written for
 
     def shared_step(self, batch, **kwargs):
         image, audio, labels = batch["image"], batch["audio"], batch["label"]
@@ -735,6 +787,29 @@ class AVMnistMixerMultiLossUQ(AVMnistMixerMultiLoss):
         out = super()._engine_eval_outputs(eng, batch, labels)
         out.update(self._engine_uncertainties(eng))
         return out
+
+    def _engine_cfg(self) -> dict:
+        cfg = super()._engine_cfg()
+        cfg.update(edl_loss=self.edl_loss, kl_weight=self.kl_weight, annealing_step=self.annealing_step)
+        return cfg
+
+    def _follow_epoch(self):
+        """Bound: the engine's lambda follows current_epoch (a host comparison; one small fill when the epoch moved)."""
+        if self._engine is not None and self._engine_epoch != self.current_epoch:
+            self._engine.set_epoch(self.current_epoch)
+            self._engine_epoch = self.current_epoch
+
+    def on_train_epoch_start(self, data=None, split: str = "train"):
+        self._follow_epoch()
+        return super().on_train_epoch_start(data, split)
+
+    def training_step(self, batch, batch_idx: int = 0):
+        self._follow_epoch()                         # (ahead of the two-stage switch, which reads current_epoch as well)
+        return super().training_step(batch, batch_idx)
+
+    def _eval_step(self, batch, mode: str):
+        self._follow_epoch()                         # the reference passes current_epoch in validation too (models/avmnist.py:503-505)
+        return super()._eval_step(batch, mode)
 
     def _make_engine(self, cfg, batch_size, device, precision, scores=False, rank_scores=False, rank_capacity=65536):
         from .engine import AVMnistUQEngine

@@ -810,14 +810,22 @@ def heads_ce(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: int
 
 
 def heads_edl(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: int, out=None, zero_losses: bool = True,
-              weights: Optional[torch.Tensor] = None):
+              weights: Optional[torch.Tensor] = None, risk: Optional[str] = None, kl_coef: Optional[torch.Tensor] = None,
+              kl_out: Optional[torch.Tensor] = None):
     """Evidential heads (m2m_heads_edl: models/avmnist.py:447-572 with modules/losses.py:5-31): heads as for heads_ce.
     Returns logits (nh, B, K), losses (nh + 1), preds (nh, B) int32 = argmax relu(logits), uncertainty (nh, B) = K / S and
     combined (B) int32, the prediction of the strictly least uncertain head (0 when there is none) -- written into `out` if given,
     where `combined` may be the last row of `preds` (that head's own predictions are then replaced).
-    weights: the heads' loss coefficients as a device tensor, None: each head's `weight`."""
+    weights: the heads' loss coefficients as a device tensor, None: each head's `weight`.
+    risk ("mse" / "ce"), kl_coef (one device float, lambda) and kl_out (nh device floats: += the unscaled batch-mean KL) select
+    m2m_heads_edl_risk (modules/losses.py:71-93, :52-68); with none of the three the call is m2m_heads_edl, as before."""
     nh = len(heads)
     _check_weights(weights, nh)
+    if risk is not None and risk not in L.EDL_RISK_BY_NAME:
+        raise ValueError(f"heads_edl: risk must be one of {', '.join(L.EDL_RISK_BY_NAME)}, got {risk!r}")
+    for name, t, n in (("kl_coef", kl_coef, 1), ("kl_out", kl_out, nh)):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.numel() < n or not t.is_contiguous()):
+            raise ValueError(f"heads_edl: {name}: a contiguous float32 device tensor of at least {n} entries")
     arr = _head_array(heads)
     dev = labels.device
     if out is not None:
@@ -828,7 +836,13 @@ def heads_edl(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: in
         preds = torch.empty(nh, B, dtype=torch.int32, device=dev)
         uncertainty = torch.empty(nh, B, device=dev)
         combined = torch.empty(B, dtype=torch.int32, device=dev)
-    L.check(L.lib().m2m_heads_edl(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(), preds.data_ptr(),
-                                  uncertainty.data_ptr(), combined.data_ptr(), int(zero_losses), L.ptr(weights), L.stream_ptr()),
-            "heads_edl")
+    if risk is None and kl_coef is None and kl_out is None:
+        L.check(L.lib().m2m_heads_edl(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(), preds.data_ptr(),
+                                      uncertainty.data_ptr(), combined.data_ptr(), int(zero_losses), L.ptr(weights), L.stream_ptr()),
+                "heads_edl")
+    else:
+        L.check(L.lib().m2m_heads_edl_risk(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(), preds.data_ptr(),
+                                           uncertainty.data_ptr(), combined.data_ptr(), int(zero_losses), L.ptr(weights),
+                                           L.EDL_RISK_BY_NAME[risk or "mse"], L.ptr(kl_coef), L.ptr(kl_out), L.stream_ptr()),
+                "heads_edl_risk")
     return logits, losses, preds, uncertainty, combined
