@@ -80,7 +80,7 @@ typedef struct m2m_tower {
     int32_t prec;          /* M2M_PREC_*                                       */
     int32_t D, N, T, C;    /* hidden_dim, num_patch, token_dim, channel_dim    */
     int32_t Cp;            /* C rounded up to a multiple of 32 (packed operands are zero-padded) */
-    int32_t nblocks;       /* <= M2M_MAX_BLOCKS                                */
+    int32_t nblocks;       /* 1 <= nblocks <= M2M_MAX_BLOCKS (a tower of no blocks is refused by every call) */
     int32_t has_final_ln;  /* 1: apply layer_norm after the blocks             */
     float p_drop;          /* nn.Dropout p of the four dropout sites of every block */
     uint32_t site_base;    /* distinguishes this tower's dropout streams       */
@@ -206,7 +206,12 @@ int m2m_embed_forward_head(const m2m_embed* e, const float* input, int B, float*
  *   training              : 1 -> dropout active and activations saved
  *   seed, step, step_dev  : dropout stream = f(seed, step + (step_dev ? *step_dev : 0), site, element); step_dev is a
  *                           device counter so that a captured hipGraph draws fresh masks on every replay
- *                           (m2m_counter_add bumps it); backward / wgrad must be given the same values */
+ *                           (m2m_counter_add bumps it); backward / wgrad must be given the same values
+ * Buffers (this call, m2m_towers_forward and the backward calls below; checked before anything is launched, -1 otherwise):
+ * the kernels move x0, out, pooled, d_out, d_pooled and d_x0 as float4, so every one of them that is given is 16-byte aligned,
+ * x0, out and d_x0 are not NULL, and every sample stride (d_out's where d_out is given) is at least N * D and, like
+ * x0_part_stride with x0_parts > 1, a multiple of 4 floats.  Only the N * D floats of a sample are read or written: whatever
+ * lies between two samples of a strided buffer (the other tower's half of a fused buffer) is left alone. */
 int m2m_tower_forward(const m2m_tower* t, const float* x0, int64_t x0_sample_stride, int B,
                       float* out, int64_t out_sample_stride, float* pooled,
                       int training, uint32_t seed, uint32_t step, const uint32_t* step_dev, void* stream);
@@ -224,7 +229,8 @@ typedef struct m2m_tower_io {
     float* out; int64_t out_sample_stride;
     float* pooled;
     int32_t x0_parts;            /* 0 / 1: x0 is the input.  2..4: the input is the sum of x0_parts buffers, part p at */
-    int64_t x0_part_stride;      /*        x0 + p * x0_part_stride floats (k-split partial sums of m2m_embeds_forward) */
+    int64_t x0_part_stride;      /*        x0 + p * x0_part_stride floats (k-split partial sums of m2m_embeds_forward).
+                                  *        More than 4 parts: -1 on the fused and the column-split path; a wide pair takes 1 only */
 } m2m_tower_io;
 int m2m_towers_forward(const m2m_tower* const* towers, const m2m_tower_io* io, int ntowers, int B, int training,
                        uint32_t seed, uint32_t step, const uint32_t* step_dev, void* stream);
@@ -245,7 +251,10 @@ int m2m_towers_forward_embeds(const m2m_tower* const* towers, const m2m_tower_io
 /* Reverse pass through final LayerNorm + blocks.
  *   d_out / d_out_sample_stride : gradient wrt the tower output tokens, or NULL
  *   d_pooled (B, D)             : gradient wrt `pooled`, or NULL (adds d_pooled/N to every token)
- *   d_x0 / d_x0_sample_stride   : gradient wrt the tower input tokens (written)
+ *                                 Both, either or neither may be given; with neither the upstream gradient is zero: d_x0 is
+ *                                 written with zeros and every accumulated gradient keeps its value.
+ *   d_x0 / d_x0_sample_stride   : gradient wrt the tower input tokens (written, not accumulated)
+ * Alignment and strides of the buffers: as for m2m_tower_forward.
  * Accumulates the LayerNorm, token-mixing and ch_b2 gradients; writes the packed operands (at_chn, dyt_chn, h_chn,
  * dh_chn) that m2m_tower_wgrad contracts into the channel-mixing weight gradients. */
 int m2m_tower_backward(const m2m_tower* t, int B, const float* d_out, int64_t d_out_sample_stride,

@@ -9,6 +9,10 @@
 void m2m_set_error(const char* msg, const char* file, int line);
 // 0, or -1 with the error set: descriptor fields the kernels are built for (precision, hidden_dim, N, T, blocks, buffers at batch B)
 int m2m_check_tower(const m2m_tower* t, int B);
+// 0, or -1 with the error set ("<call>: <argument> ..."): the caller's buffers of a forward (f) and / or backward (g) call of tower t,
+// before the call chooses a path -- x0, out and d_x0 given; every buffer (pooled, d_out and d_pooled where given) 16-byte aligned;
+// sample strides (d_out's where d_out is given) at least N * D and, as x0_part_stride with x0_parts > 1, multiples of 4 floats
+int m2m_check_tower_io(const char* call, const m2m_tower* t, const m2m_tower_io* f, const m2m_tower_gio* g);
 
 // (grid and packed-image sizes in api.hip, pack.hip, adam.hip and probes.hip)
 static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }

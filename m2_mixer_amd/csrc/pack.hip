@@ -59,7 +59,6 @@ __global__ void pack_tower_kernel(const m2m_tower tw) {
 
 extern "C" int m2m_pack_tower(const m2m_tower* t, void* stream) {
     if (int rc = m2m_check_tower(t, 1)) return rc;
-    if (t->nblocks == 0) return 0;
     const long KB = t->prec == PREC_BF16 ? 32 : 16;
     const long nslots = (long)(t->Cp / 16) * (t->D / KB) * 64;
     const long need = nslots > t->Cp ? nslots : t->Cp;

@@ -67,6 +67,8 @@ int m2m_split_forward(const m2m_tower* const* towers, const m2m_tower_io* io, in
                       unsigned int step, const unsigned int* step_dev, hipStream_t st) {
     const m2m_tower* t0 = towers[0];
     const int nb = t0->nblocks, S = split_count(t0);
+    for (int i = 0; i < ntow; ++i)
+        if (io[i].x0_parts > 4) { m2m_set_error("towers_forward: at most 4 input parts", __FILE__, __LINE__); return -1; }
     for (int b = 0; b <= nb; ++b) {
         SplitMixArgs m;
         memset(&m, 0, sizeof(m));

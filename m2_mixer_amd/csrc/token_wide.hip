@@ -911,10 +911,6 @@ int m2m_forward_wide(const m2m_tower* t, const float* x0, long x0_ss, int B, flo
                      int training, unsigned int seed, unsigned int step, const unsigned int* step_dev, hipStream_t st) {
     const long dense = (long)t->N * t->D;
     if (!t->ws_a || !t->ws_b) { m2m_set_error("wide path (N > 8 or D > 128) needs the ws_a / ws_b workspaces", __FILE__, __LINE__); return -1; }
-    if (t->nblocks == 0) {      // final LayerNorm only
-        m2m_tower v = *t;
-        if (int rc = m2m_chain_forward_rows(&v, x0, x0_ss, B, out, out_ss, training, seed, step, step_dev, st)) return rc;
-    }
     const float* src = x0;
     long src_ss = x0_ss;
     for (int b = 0; b < t->nblocks; ++b) {
@@ -944,10 +940,6 @@ int m2m_backward_wide(const m2m_tower* t, int B, const float* d_out, long d_out_
     const long dense = (long)t->N * t->D;
     const long rows = (long)B * t->N;
     if (!t->ws_a || !t->ws_b) { m2m_set_error("wide path (N > 8 or D > 128) needs the ws_a / ws_b workspaces", __FILE__, __LINE__); return -1; }
-    if (t->nblocks == 0) {
-        m2m_tower v = *t;
-        return m2m_chain_backward_rows(&v, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);
-    }
     const float* up = d_out;
     long up_ss = d_out_ss;
     const float* up_pooled = d_pooled;

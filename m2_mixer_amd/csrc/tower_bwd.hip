@@ -1358,9 +1358,11 @@ int m2m_chain_backward_rows_group(const m2m_tower* const* v, int B, const float*
 extern "C" int m2m_towers_backward(const m2m_tower* const* towers, const m2m_tower_gio* io, int ntowers, int B, uint32_t seed,
                                    uint32_t step, const uint32_t* step_dev, void* stream) {
     if (!towers || !io || ntowers != 2) { m2m_set_error("towers_backward: exactly two towers per launch", __FILE__, __LINE__); return -1; }
-    if (int rc = bwd_split_mode_init(reinterpret_cast<hipStream_t>(stream))) return rc;
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i) {
         if (int rc = m2m_check_tower(towers[i], B)) return rc;
+        if (int rc = m2m_check_tower_io("towers_backward", towers[i], nullptr, &io[i])) return rc;
+    }
+    if (int rc = bwd_split_mode_init(reinterpret_cast<hipStream_t>(stream))) return rc;
     // the forward of this step took the split path under the same conditions (csrc/split.h)
     if (m2m_split_eligible(towers[0], B, 1) && m2m_split_eligible(towers[1], B, 1) && m2m_split_can_group(towers[0], towers[1]))
         return m2m_split_backward(towers, io, 2, B, seed, step, step_dev, reinterpret_cast<hipStream_t>(stream));
@@ -1472,14 +1474,13 @@ extern "C" int m2m_tower_backward_heads(const m2m_tower* t, int B, const m2m_hea
 extern "C" int m2m_tower_backward(const m2m_tower* t, int B, const float* d_out, int64_t d_out_ss, const float* d_pooled,
                                   float* d_x0, int64_t d_x0_ss, uint32_t seed, uint32_t step, const uint32_t* step_dev, void* stream) {
     if (int rc = m2m_check_tower(t, B)) return rc;
+    m2m_tower_gio io1;
+    io1.d_out = d_out; io1.d_out_sample_stride = d_out_ss; io1.d_pooled = d_pooled; io1.d_x0 = d_x0; io1.d_x0_sample_stride = d_x0_ss;
+    if (int rc = m2m_check_tower_io("tower_backward", t, nullptr, &io1)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (int rc = bwd_split_mode_init(st)) return rc;
     if (m2m_is_wide(t)) return m2m_backward_wide(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);
-    if (m2m_split_eligible(t, B, 1)) {
-        m2m_tower_gio io1;
-        io1.d_out = d_out; io1.d_out_sample_stride = d_out_ss; io1.d_pooled = d_pooled; io1.d_x0 = d_x0; io1.d_x0_sample_stride = d_x0_ss;
-        return m2m_split_backward(&t, &io1, 1, B, seed, step, step_dev, st);
-    }
+    if (m2m_split_eligible(t, B, 1)) return m2m_split_backward(&t, &io1, 1, B, seed, step, step_dev, st);
     const int rc = m2m_dispatch_pd(m2m_fused_dims{}, t->prec, t->D, [&](auto P, auto D) {
         return m2m_fused_class(t->N, t->T, [&](auto NMAX, auto TG) {
             return launch_bwd<P(), D(), NMAX(), TG()>(t, B, d_out, d_out_ss, d_pooled, d_x0, d_x0_ss, seed, step, step_dev, st);

@@ -662,8 +662,10 @@ static int towers_forward_impl(const m2m_tower* const* towers, const m2m_tower_i
                                const float* const* inputs, const m2m_step_head* head, int B, int training,
                                uint32_t seed, uint32_t step, const uint32_t* step_dev, void* stream) {
     if (!towers || !io || ntowers != 2) { m2m_set_error("towers_forward: exactly two towers per launch", __FILE__, __LINE__); return -1; }
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i) {
         if (int rc = m2m_check_tower(towers[i], B)) return rc;
+        if (int rc = m2m_check_tower_io("towers_forward", towers[i], &io[i], nullptr)) return rc;
+    }
     // large batches: per-block launches with column-split channel mixing (csrc/split.h)
     if (m2m_split_eligible(towers[0], B, training) && m2m_split_eligible(towers[1], B, training) &&
         m2m_split_can_group(towers[0], towers[1]))
@@ -708,14 +710,13 @@ static int towers_forward_impl(const m2m_tower* const* towers, const m2m_tower_i
 extern "C" int m2m_tower_forward(const m2m_tower* t, const float* x0, int64_t x0_ss, int B, float* out, int64_t out_ss,
                                  float* pooled, int training, uint32_t seed, uint32_t step, const uint32_t* step_dev, void* stream) {
     if (int rc = m2m_check_tower(t, B)) return rc;
+    m2m_tower_io io1;
+    io1.x0 = x0; io1.x0_sample_stride = x0_ss; io1.out = out; io1.out_sample_stride = out_ss; io1.pooled = pooled;
+    io1.x0_parts = 1; io1.x0_part_stride = 0;
+    if (int rc = m2m_check_tower_io("tower_forward", t, &io1, nullptr)) return rc;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (m2m_is_wide(t)) return m2m_forward_wide(t, x0, x0_ss, B, out, out_ss, pooled, training, seed, step, step_dev, st);
-    if (m2m_split_eligible(t, B, training)) {
-        m2m_tower_io io1;
-        io1.x0 = x0; io1.x0_sample_stride = x0_ss; io1.out = out; io1.out_sample_stride = out_ss; io1.pooled = pooled;
-        io1.x0_parts = 1; io1.x0_part_stride = 0;
-        return m2m_split_forward(&t, &io1, 1, B, training, seed, step, step_dev, st);
-    }
+    if (m2m_split_eligible(t, B, training)) return m2m_split_forward(&t, &io1, 1, B, training, seed, step, step_dev, st);
     const int rc = m2m_dispatch_pd(m2m_fused_dims{}, t->prec, t->D, [&](auto P, auto D) {
         return m2m_fused_class(t->N, t->T, [&](auto NMAX, auto) {
             return launch_fwd<P(), D(), NMAX()>(t, x0, x0_ss, B, out, out_ss, pooled, training, seed, step, step_dev, st);

@@ -677,7 +677,6 @@ extern "C" int m2m_wgrad_slot_groups(const m2m_tower* const* towers, int ntowers
 
 extern "C" int m2m_tower_wgrad(const m2m_tower* t, int B, uint32_t seed, uint32_t step, const uint32_t* step_dev, void* stream) {
     if (int rc = m2m_check_tower(t, B)) return rc;
-    if (t->nblocks == 0) return 0;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     if (t->wgrad_flags & M2M_WGRAD_REDUCES_SMALL) {              // the deferred slot reduction of this tower's backward: its own launch here
         SplitReduceArgs one;

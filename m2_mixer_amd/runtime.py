@@ -81,6 +81,9 @@ class TowerRuntime:
 
     def __init__(self, D: int, N: int, T: int, Cc: int, nblocks: int, has_final_ln: bool, p_drop: float,
                  prec: int, site_base: int = 0):
+        if nblocks < 1:
+            raise RuntimeError("one m2m_tower holds at least one block: the kernels have no final-LayerNorm-only form "
+                               "(include/m2mixer.h: 1 <= nblocks <= M2M_MAX_BLOCKS)")
         if nblocks > L.MAX_BLOCKS:
             raise RuntimeError(f"one m2m_tower holds at most {L.MAX_BLOCKS} blocks; deeper towers are a chain of them "
                                "(modules/mixer.py does that; the fused engines take towers of up to 8 blocks)")
@@ -125,7 +128,7 @@ class TowerRuntime:
                 ptrs.append(t.data_ptr())
                 vers.append(t._version)
             self._keep["lnf"] = tuple(lnf)
-        self.device = blocks[0]["ln1_w"].device if blocks else lnf[0].device
+        self.device = blocks[0]["ln1_w"].device
         self._param_ptrs, self._param_versions = ptrs, vers
         self._packed_for = None            # new storage: whatever the packed copies hold belongs to the old one
         self._ensure_packed_buffers()
@@ -138,7 +141,7 @@ class TowerRuntime:
         return ptrs != self._param_ptrs
 
     def _ensure_packed_buffers(self):
-        if "packed0" in self._keep or self.nblocks == 0:
+        if "packed0" in self._keep:
             return
         nb = L.packed_bytes(self.prec, self.Cp, self.D)
         for i in range(self.nblocks):
@@ -243,7 +246,7 @@ class TowerRuntime:
         """Buffers of the split path (include/m2mixer.h, csrc/split.h): slabs of the column-split channel launches, the carry
         stream, per-block bf16 operand images.  Allocated for every tower the split path can take (fused class, bf16,
         hidden_dim 128); whether a call uses it is the library's decision (batch size; M2M_SPLIT=0/1 overrides)."""
-        if self.wide or self.prec != L.PREC_BF16 or self.D != 128 or self.nblocks == 0 or B == self._splitB:
+        if self.wide or self.prec != L.PREC_BF16 or self.D != 128 or B == self._splitB:
             return
         M = B * self.N
         # the mix launches' 16-row tiles hold whole samples: the operand images and the slabs have 16 rows per tile, which is
@@ -326,7 +329,7 @@ class TowerRuntime:
         """Let the backward also leave d_x0^T as packed operand blocks (m2m_tower.dx0_chn): the patch-embedding weight
         gradient of the tower's embedding then takes the single-owner form (towers_wgrad(..., embed_towers=...)).  Fused-path
         bf16 towers only."""
-        if self.wide or self.prec != L.PREC_BF16 or self.nblocks == 0:
+        if self.wide or self.prec != L.PREC_BF16:
             return False
         self._keep["want_dx0_image"] = True
         self._bufB = 0                       # (re)allocate with the image
@@ -364,7 +367,7 @@ class TowerRuntime:
         """Partial-gradient slot of every block (second row group of the weight-gradient launch), each with the 16-byte
         phase of its flat-gradient range so that the optimizer can add it with vector loads."""
         rng = self.channel_grad_ranges(flat_g)
-        if rng is None or self.nblocks == 0:
+        if rng is None:
             return False
         n = rng[0][1]
         buf = torch.zeros(self.nblocks * (n + 8), device=self.device)
@@ -399,7 +402,7 @@ class TowerRuntime:
     def has_small_slots(self) -> bool:
         """The fused backward of this tower can collect its small parameter gradients in per-workgroup slots (ensure_split
         allocates them; csrc/tower_bwd.hip: m2m_small_part)."""
-        return (not self.wide and self.prec == L.PREC_BF16 and self.D == 128 and self.nblocks > 0
+        return (not self.wide and self.prec == L.PREC_BF16 and self.D == 128
                 and 2 * self.T * self.N + self.T + self.N <= 576)
 
     def set_wgrad_group_slots(self, on: bool):

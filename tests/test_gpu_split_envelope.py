@@ -262,40 +262,79 @@ SEED = 1234
 
 
 class PairTower:
-    """One FusionMixer-shaped tower (blocks + final LayerNorm) driven through the runtime, with its float64 twin."""
+    """One tower (blocks + optional final LayerNorm) driven through the runtime, with its float64 twin.
 
-    def __init__(self, tow, seed, site_base, dev, parts=1, pooled=False):
+    Defaults: a FusionMixer-shaped bf16 tower on dense buffers, fed `parts` k-split input parts and read out through its output
+    or (pooled) its token mean.  tests/test_gpu_tower_io.py also sets has_final_ln, the precision, pads (floats behind every
+    sample of x0 / out / d_out / d_x0, filled with the index-carrying NaN of nan_fill) and inputs = (params, xparts, d_out,
+    d_pooled) of its own; `up` then names the upstream gradients the backward is given ("out", "pooled", "both", "none")."""
+
+    def __init__(self, tow, seed, site_base, dev, parts=1, pooled=False, has_final_ln=True, prec="bf16", pads=None, inputs=None,
+                 up=None):
         from m2_mixer_amd import _lib as L
         from m2_mixer_amd.runtime import BLOCK_FIELDS, BLOCK_KEYS, TowerRuntime
-        self.tow, self.parts, self.pooled, self.dev = tow, parts, pooled, dev
+        self.tow, self.parts, self.pooled, self.dev, self.has_final_ln = tow, parts, pooled, dev, has_final_ln
+        self.up_form = up if up is not None else ("pooled" if pooled else "out")
         cfg = dict(hidden_dim=tow.D, token_dim=tow.T, channel_dim=tow.C, num_mixers=tow.nb)
-        self.params = G.make_params(G.tower_shapes("", cfg, tow.N, "none"), seed)
+        self.keys = [f"mixer_blocks.{i}.{BLOCK_KEYS[f]}" for i in range(tow.nb) for f in BLOCK_FIELDS]
+        self.keys += ["layer_norm.weight", "layer_norm.bias"] if has_final_ln else []
+        B, N, D = tow.B, tow.N, tow.D
+        if inputs is None:
+            params = G.make_params(G.tower_shapes("", cfg, tow.N, "none"), seed)
+            rng = np.random.default_rng(seed + 1)
+            f32 = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32))
+            xparts = f32(parts, B, N, D)                         # the tower input is the sum of the parts
+            up_t = f32(B, D) if pooled else f32(B, N, D)         # upstream gradient (of the token mean, or of the output)
+            d_out, d_pool = (None, up_t) if pooled else (up_t, None)
+        else:
+            params, xparts, d_out, d_pool = inputs
+            xparts = xparts[:parts]
+        self.params = {k: params[k] for k in self.keys}
         self.dparams = {k: v.to(dev) for k, v in self.params.items()}
-        self.rt = rt = TowerRuntime(tow.D, tow.N, tow.T, tow.C, tow.nb, True, tow.p, L.PREC_BF16, site_base)
+        self.rt = rt = TowerRuntime(tow.D, tow.N, tow.T, tow.C, tow.nb, has_final_ln, tow.p, L.PREC_BY_NAME[prec], site_base)
         blocks = [{f: self.dparams[f"mixer_blocks.{i}.{BLOCK_KEYS[f]}"] for f in BLOCK_FIELDS} for i in range(tow.nb)]
-        rt.bind_params(blocks, (self.dparams["layer_norm.weight"], self.dparams["layer_norm.bias"]))
+        rt.bind_params(blocks, (self.dparams["layer_norm.weight"], self.dparams["layer_norm.bias"]) if has_final_ln else None)
         rt.pack(force=True)
-        self.keys = [f"mixer_blocks.{i}.{BLOCK_KEYS[f]}" for i in range(tow.nb) for f in BLOCK_FIELDS] + ["layer_norm.weight", "layer_norm.bias"]
         self.flat = torch.zeros(rt.grad_numel(), device=dev)
         self.views = rt.bind_grads(self.flat)
-        B, N, D = tow.B, tow.N, tow.D
-        rng = np.random.default_rng(seed + 1)
-        f32 = lambda *s: torch.from_numpy(rng.standard_normal(s).astype(np.float32))
-        self.xparts = f32(parts, B, N, D)                        # the tower input is the sum of the parts
-        self.up = f32(B, D) if pooled else f32(B, N, D)          # upstream gradient (of the token mean, or of the output)
-        self.xdev, self.updev = self.xparts.to(dev), self.up.to(dev)
-        self.out, self.pool = torch.zeros(B, N, D, device=dev), torch.zeros(B, D, device=dev)
-        self.dx = torch.zeros(B, N, D, device=dev)
+        self.xparts, self.d_out, self.d_pool = xparts, d_out, d_pool
+        self.up = d_pool if pooled else d_out
+        pads = dict(pads or {})
+        # every caller buffer: (.., B, N D + pad) storage, the (.., B, N, D) view the samples live in, the sample stride
+        self.bufs, self.before = {}, {}
+        self.xdev, self.x_ss = self._buffer("x0", pads, xparts)
+        self.out, self.out_ss = self._buffer("out", pads, torch.zeros(B, N, D))
+        self.dx, self.dx_ss = self._buffer("d_x0", pads, torch.zeros(B, N, D))
+        self.d_out_dev, self.d_out_ss = self._buffer("d_out", pads, d_out) if d_out is not None else (None, N * D)
+        self.d_pool_dev = d_pool.to(dev) if d_pool is not None else None
+        self.updev = self.d_pool_dev if pooled else self.d_out_dev
+        self.pool = torch.zeros(B, D, device=dev)
         rt.ensure_buffers(B)
         rt.ensure_workspace(B)
 
+    def _buffer(self, name, pads, values):
+        N, D = self.tow.N, self.tow.D
+        pad = pads.get(name, 0)
+        buf = torch.zeros(*values.shape[:-2], N * D + pad, device=self.dev)
+        self.before[name] = nan_fill(buf) if pad else None
+        view = buf[..., :N * D].view(*values.shape)
+        view.copy_(values.to(self.dev))
+        self.bufs[name] = buf
+        return view, N * D + pad
+
+    def pads_untouched(self, name):
+        """Every pad word of a strided buffer still holds the bits it was filled with."""
+        n = self.tow.N * self.tow.D
+        return self.before[name] is None or torch.equal(self.bufs[name].view(torch.int32)[..., n:], self.before[name][..., n:])
+
     def fwd_io(self):
-        B, N, D = self.tow.B, self.tow.N, self.tow.D
-        return (self.xdev, N * D, self.out, N * D, self.pool if self.pooled else None, self.parts, B * N * D)
+        B = self.tow.B
+        return (self.xdev, self.x_ss, self.out, self.out_ss, self.pool if self.pooled else None, self.parts, B * self.x_ss)
 
     def bwd_io(self):
-        N, D = self.tow.N, self.tow.D
-        return (None if self.pooled else self.updev, N * D, self.updev if self.pooled else None, self.dx, N * D)
+        d_out = self.d_out_dev if self.up_form in ("out", "both") else None
+        d_pool = self.d_pool_dev if self.up_form in ("pooled", "both") else None
+        return (d_out, self.d_out_ss, d_pool, self.dx, self.dx_ss)
 
     def result(self):
         return (self.pool if self.pooled else self.out).clone(), self.dx.clone(), self.flat.clone()
