@@ -663,6 +663,34 @@ int m2m_epoch_accumulate(const float* losses, int nloss, const int32_t* preds, c
  * step count of m2m_epoch_accumulate.  One workgroup, no atomics, a fixed summation order.  -1 on a NULL pointer, nheads < 1, B < 1. */
 int m2m_epoch_accumulate_uq(const float* uncertainty, int nheads, int B, double* sums, void* stream);
 
+/* ---- prediction record: an evaluation step appends its own outputs (additive within ABI 18; csrc/record.hip) ---------------------
+ * The reference's test_epoch_end concatenates every test step's preds, preds_<a>, preds_<b>, labels and three logits tensors on the
+ * host and writes them to test_preds.pt (models/avmnist.py:382-398, models/mmimdb.py:194-209).  With the record's buffers and a
+ * cursor in device memory, one launch behind the step's heads appends the step's rows: a captured evaluation step takes no argument
+ * from the host, and the split's predictions are read back once.
+ *
+ * state: M2M_RECORD_STATE_WORDS uint32 in device memory, zeroed by the caller to empty the record:
+ *   [0] rows appended since the last clear (keeps counting past capacity; 32 bits)
+ *   [1] reserved, zero
+ *   [2] reserved, zero
+ *   [3] rows dropped: every append adds the rows of its batch that fell at or past capacity
+ *
+ *   m2m_record_append   the mirror image of m2m_feed_gather: for every source and every batch row r < B, row r of `src` (a step's
+ *                       output buffer: B rows of row_bytes bytes, back to back) is copied to row state[0] + r of `dst` (the record's
+ *                       buffer of `capacity` such rows).  The cursor is read from `state` on the device; a one-thread launch
+ *                       enqueued behind the copy by the same call advances it by B -- stream order keeps it behind every read of
+ *                       the cursor.  A row at or past `capacity` is never written: a step that straddles the capacity writes its
+ *                       rows below it and drops the rest, and every dropped row is counted in state[3].  A pure copy: no float
+ *                       arithmetic, no LDS, no atomics; 16 bytes per lane where row_bytes, src and dst are multiples of 16 (every
+ *                       destination row is then 16-byte aligned whatever the cursor is), else 4.  `srcs` is host memory, read
+ *                       before the call returns (a captured graph keeps the descriptors by value).
+ * Returns -1 (m2m_last_error) and launches nothing on: NULL srcs or state; nsrc outside [1, M2M_RECORD_MAX_SOURCES]; B < 1;
+ * capacity < 1; a NULL src or dst; row_bytes not a positive multiple of 4; a src or dst that is not 4-byte aligned;
+ * B * row_bytes / 4 >= 2^31. */
+#define M2M_RECORD_MAX_SOURCES 16
+#define M2M_RECORD_STATE_WORDS 4
+int m2m_record_append(const m2m_feed_src* srcs, int nsrc, int B, int64_t capacity, uint32_t* state, void* stream);
+
 /* ---- test hooks ----------------------------------------------------------------------------------- */
 /* keep-mask (uint8, 1 keep) the kernels use for dropout site `site` (0 tok hidden, 1 tok out,
  * 2 channel hidden, 3 channel out) of block `blk` of tower t at (seed, step): rows x cols elements with

@@ -103,6 +103,7 @@ FEED_MAX_SOURCES, FEED_STATE_WORDS = 4, 4          # m2m_feed_gather (M2M_FEED_M
 EDL_MSE, EDL_CE = 0, 1                             # m2m_heads_edl_risk's `risk` (M2M_EDL_MSE, M2M_EDL_CE)
 EDL_RISK_BY_NAME = {"mse": EDL_MSE, "ce": EDL_CE}
 FEED_MUTE_STATE_WORDS = 2                          # m2m_feed_gather_muted: step index, steps past the schedule
+RECORD_MAX_SOURCES, RECORD_STATE_WORDS = 16, 4     # m2m_record_append (M2M_RECORD_MAX_SOURCES, M2M_RECORD_STATE_WORDS)
 
 
 class FeedSrc(C.Structure):
@@ -207,6 +208,8 @@ SIGNATURES = {
     "m2m_feed_gather_muted": (C.c_int, [C.POINTER(FeedSrc), C.c_int, _fp, C.c_int, _fp, _fp, C.c_int, _fp, _fp]),
     "m2m_epoch_accumulate": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp]),
     "m2m_epoch_accumulate_uq": (C.c_int, [_fp, C.c_int, C.c_int, _fp, _fp]),
+    # prediction record (csrc/record.hip): an evaluation step appends its logits, predictions and labels at a device-side cursor
+    "m2m_record_append": (C.c_int, [C.POINTER(FeedSrc), C.c_int, C.c_int, C.c_int64, _fp, _fp]),
     "m2m_mlp_forward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, C.c_int, C.c_uint32, C.c_uint32,
                                   _fp, _fp]),
     "m2m_mlp_backward": (C.c_int, [C.POINTER(Mlp), _fp, C.c_int, _fp, C.c_int64, _fp, _fp]),

@@ -1,10 +1,11 @@
 """Device-side accumulators of the fused engines (engine.py): what a step adds to beside its own work, read back once per epoch.
   ScoreTable   integer count table of one split (csrc/scores.hip)      -> accuracy / precision / recall / F1 (scores.py)
   RankBuffer   softmax rows and labels of one split (csrc/rank.hip)    -> average precision / ROC-AUC (scores.py)
+  PredictionRecord  logits, predictions and labels of one split, row by row (csrc/record.hip) -> the reference's test_preds.pt
   EpochFeed    one split's resident tensors behind a device-side order and cursor, with the epoch's loss sums and hit counts
                (csrc/feed.hip); engine.capture_feed captures steps that feed themselves from it
-Of an engine they use `losses`, `preds` and `B` only: this module imports the library (_lib) and scores, never engine, which
-re-exports the three classes.
+Of an engine they use `losses`, `logits`, `preds`, `uncertainty` and `B` only: this module imports the library (_lib) and scores,
+never engine, which re-exports the classes.
 """
 from __future__ import annotations
 
@@ -129,6 +130,119 @@ class RankBuffer:
         from . import scores as S
         counts, labels = self.counts()
         return S.task_rank_scores(self.task, counts.numpy(), labels.numpy(), self.K, self.head_names, names)
+
+
+def record_key_names(task: str, head_names: Sequence[str]) -> Dict[str, Tuple[str, ...]]:
+    """The names PredictionRecord.read() gives the per-head rows of `task` (head order: modality a, modality b, fusion): the keys
+    of the engines' _eval_outputs and of a bound module's test_step.  {"logits": (...), "preds": (...), "uncertainty": (...)}; the
+    fusion head carries the plain name.  MIMIC spells its logits `logits_<modality>` (models/mimic.py:126-129), the two-tower
+    models `<modality>_logits` (models/avmnist.py:303-312).  A pure function."""
+    a, b = head_names[0], head_names[1]
+    logits = (f"logits_{a}", f"logits_{b}", "logits") if task == "mimic" else (f"{a}_logits", f"{b}_logits", "logits")
+    return {"logits": logits, "preds": (f"preds_{a}", f"preds_{b}", "preds"),
+            "uncertainty": (f"uncertainty_{a}", f"uncertainty_{b}", "uncertainty")}
+
+
+class PredictionRecord:
+    """The prediction record of one split in device memory (csrc/record.hip): every evaluation step APPENDS
+    its logits, its predictions and its labels -- on the evidential engine its per-sample uncertainties too -- at a row cursor that
+    lives in `state` on the device (m2m_record_append: one copy launch and a one-thread advance, capturable), and the host reads
+    the split's rows once: what the reference's test_epoch_end concatenates on the host and dumps as test_preds.pt
+    (models/avmnist.py:382-398, models/mmimdb.py:194-209).  Rows are in arrival order.  Allocated once: captured graphs keep the
+    pointers.
+      logits       (nheads, capacity, K) float32
+      preds        (nheads, capacity) int32; multilabel (MM-IMDb): (nheads, capacity, K) int32
+      labels       (capacity) int64; multilabel: (capacity, K) float32
+      uncertainty  (nheads, capacity) float32 -- uncertainty=True (AVMnistUQEngine) only
+      state        L.RECORD_STATE_WORDS uint32 (held as int32): rows appended (keeps counting past capacity), reserved, reserved,
+                   rows dropped
+    A row at or past `capacity` is never written; read() then raises."""
+
+    def __init__(self, task: str, head_names: Sequence[str], K: int, capacity: int, device, uncertainty: bool = False):
+        from . import scores as S
+        self.task, self.kind, self.head_names, self.K = task, S.TASK_KIND[task], tuple(head_names), int(K)
+        self.capacity = int(capacity)
+        if self.K < 1:
+            raise RuntimeError(f"PredictionRecord: K = {K}: at least one class")
+        if self.capacity < 1:
+            raise RuntimeError(f"PredictionRecord: capacity = {capacity}: at least one row")
+        nh, ml, dev = len(self.head_names), self.kind == "multilabel", torch.device(device)
+        if nh * (3 if uncertainty else 2) + 1 > L.RECORD_MAX_SOURCES:
+            raise RuntimeError(f"PredictionRecord: {nh} heads need more than the {L.RECORD_MAX_SOURCES} sources of one append")
+        self.names = record_key_names(task, self.head_names)
+        self.logits = torch.zeros(nh, self.capacity, self.K, device=dev)
+        self.preds = torch.zeros((nh, self.capacity, self.K) if ml else (nh, self.capacity), dtype=torch.int32, device=dev)
+        self.labels = (torch.zeros(self.capacity, self.K, device=dev) if ml
+                       else torch.zeros(self.capacity, dtype=torch.int64, device=dev))
+        self.uncertainty = torch.zeros(nh, self.capacity, device=dev) if uncertainty else None
+        self.state = torch.zeros(L.RECORD_STATE_WORDS, dtype=torch.int32, device=dev)
+        self.dropped = None                          # rows dropped as of the last read()
+
+    @property
+    def save_keys(self) -> Tuple[str, ...]:
+        """The keys save() writes, in the order of the reference's dump (models/avmnist.py:382-398: the task modules'
+        TEST_PRED_KEYS)."""
+        lg, pr = self.names["logits"], self.names["preds"]
+        return (pr[2], pr[0], pr[1], "labels", lg[0], lg[1], lg[2])
+
+    def add(self, engine, labels: torch.Tensor):
+        """Enqueue the append of `engine`'s step: its `logits` and `preds` -- and `uncertainty` where the record holds one -- one
+        source per head and tensor, plus `labels`.  One m2m_record_append; nothing synchronises."""
+        nh, B, K, ml, dev = len(self.head_names), int(engine.B), self.K, self.kind == "multilabel", self.state.device
+        want = [("logits", engine.logits, (nh, B, K), torch.float32),
+                ("preds", engine.preds, (nh, B, K) if ml else (nh, B), torch.int32)]
+        if self.uncertainty is not None:
+            want.append(("uncertainty", getattr(engine, "uncertainty", None), (nh, B), torch.float32))
+        want.append(("labels", labels, (B, K) if ml else (B,), torch.float32 if ml else torch.int64))
+        for name, t, shape, dtype in want:
+            if (t is None or tuple(t.shape) != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
+                got = "None" if t is None else f"{tuple(t.shape)} {t.dtype} on {t.device}"
+                raise RuntimeError(f"PredictionRecord.add: {name} must be a contiguous {dtype} tensor {shape} on {dev}, got {got}")
+        pairs = []
+        for name, t, _, _ in want[:-1]:
+            mine = getattr(self, name)
+            pairs += [(t[h], mine[h]) for h in range(nh)]
+        pairs.append((labels, self.labels))
+        desc = (L.FeedSrc * len(pairs))()
+        for d, (s, t) in zip(desc, pairs):
+            d.src, d.dst, d.row_bytes = s.data_ptr(), t.data_ptr(), int(s[0].numel()) * s.element_size()
+        L.check(L.lib().m2m_record_append(desc, len(pairs), B, self.capacity, self.state.data_ptr(), L.stream_ptr()), "record_append")
+
+    def reset(self):
+        """Empty the record: an asynchronous fill of `state` on the current stream, in place -- captured graphs keep appending
+        into the same memory (the rows behind the cursor are dead)."""
+        self.state.zero_()
+
+    def rows(self) -> int:
+        """Rows appended since the last reset (one small device-to-host copy; may exceed `capacity`: see read)."""
+        return int(self.state[0].item()) & 0xFFFFFFFF
+
+    def read(self) -> Dict[str, torch.Tensor]:
+        """The record on the host under the names the task's test_step returns: per-head logits (n, K) float32 and preds, `labels`,
+        on the evidential engine per-sample `uncertainty*` (n) -- with the dtypes a bound module's test_step gives: preds int64
+        (MIMIC: `preds*` are the softmax of the recorded logits, models/mimic.py:126), labels as recorded.  No loss keys: losses
+        are per step, not per row.  Reads `state`, then copies the first n rows of every buffer: the only synchronisation."""
+        st = self.state.cpu().numpy().view("uint32")
+        n, self.dropped = int(st[0]), int(st[3])
+        if n > self.capacity or self.dropped:
+            raise RuntimeError(f"PredictionRecord: overflow: capacity {self.capacity} rows, {n} rows seen since the last reset "
+                               f"({self.dropped} dropped; record_capacity= / prediction_record(split, capacity) sets the capacity)")
+        logits = self.logits[:, :n].cpu()
+        out = dict(zip(self.names["logits"], logits.unbind(0)))
+        if self.task == "mimic":
+            out.update(zip(self.names["preds"], torch.softmax(logits, dim=2).unbind(0)))
+        else:
+            out.update(zip(self.names["preds"], self.preds[:, :n].cpu().long().unbind(0)))
+        out["labels"] = self.labels[:n].cpu()
+        if self.uncertainty is not None:
+            out.update(zip(self.names["uncertainty"], self.uncertainty[:, :n].cpu().unbind(0)))
+        return out
+
+    def save(self, path: str, keys: Optional[Sequence[str]] = None) -> str:
+        """torch.save of read()'s `keys` (default: save_keys, the reference's dump) as one dict, in that order."""
+        got = self.read()
+        torch.save({k: got[k].clone() for k in (self.save_keys if keys is None else keys)}, path)
+        return path
 
 
 class EpochFeed:

@@ -252,7 +252,7 @@ def feed_plan(n: int, batch_size: int, steps: int, drop_last: bool = False) -> T
 
 
 def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = True, tail_engine=None, drop_last: bool = False,
-                  order=None, split: str = "train", muting=None, probe: bool = False) -> Dict[str, float]:
+                  order=None, split: str = "train", muting=None, probe: bool = False, record=None) -> Dict[str, float]:
     """run_epoch with the batches fetched on the device (engine.EpochFeed): one pass over the first `n`
     samples (default: all) of `order` (an index tensor for feed.start; None: the split's own order), every sample exactly once,
     in order.  Any of the engines; single GPU.
@@ -262,7 +262,14 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
     first slots), then the ragged tail through `tail_engine` (default: the engine's kept training sibling of that size, which
     must exist before the capture -- prepare_tail_engine's rule -- or engine.sibling(tail)), fed by gather_into, with pack()
     before and after, as run_epoch does.  Nothing is read back until the end.
-    train=False: `replay` is unused (None); every batch is gathered eagerly, evaluated and accumulated.
+    train=False: `replay` None: every batch is gathered eagerly, evaluated and accumulated.  `replay` from
+    engine.capture_feed_eval(feed, steps, scores=, rank=, record=): feed_plan(n, B, steps) replays of the graph, then the full batches
+    that do not fill a graph one at a time, eagerly, on the graph's first slots, then the ragged tail through an evaluating sibling
+    -- all into the same table, ranking buffer and record.  The graph must have been captured on this feed and with the table, the
+    ranking buffer and the record this pass uses (the engine's own of `split`, and `record`): anything else is refused by name.  A
+    training graph is refused in an evaluation pass, and an evaluation graph in a training pass.
+    record (train=False): an engine.PredictionRecord (engine.prediction_record(split, capacity)) every evaluated batch is appended
+    to; emptied here at the start, left for the caller to read().
     probe=True (with train=False): engine.probe in place of engine.evaluate -- the training-mode forward (dropout on, the stage's
     training coefficients) that updates nothing: GradBlend's loss sums (modules/gradblend.py:43-60).  Score tables and ranking
     buffers are not fed by a probing pass.
@@ -283,29 +290,52 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
     which = "train" if train else (split if split != "train" else "train_eval")
     table = engine.score_table(which) if getattr(engine, "scores", None) is not None else None
     rank = engine.rank_buffer(which) if getattr(engine, "rank", None) is not None else None
-    for t in (table, rank):
+    if record is not None and (train or probe):
+        raise ValueError("run_epoch_fed: record= goes with an evaluating pass (train=False, probe=False)")
+    for t in (table, rank, record):
         if t is not None:
             t.reset()
     extra = {} if table is None else {"scores": table}
     if rank is not None:
         extra["rank"] = rank
+    if record is not None:
+        extra["record"] = record
     feed.bind(engine)
     if muting is not None and not train:
         raise ValueError("run_epoch_fed: evaluation never mutes (muting= goes with train=True)")
     if probe and train:
         raise ValueError("run_epoch_fed: probe=True goes with train=False (a probing pass updates nothing)")
-    feed.start(order, muting=muting)
-    steps = replay.steps if train else 1
-    replays, singles, tail = feed_plan(n, B, steps, drop_last)
-    if train:
+    if replay is not None:
+        if bool(getattr(replay, "eval", False)) == train:
+            kinds = ("a training graph (engine.capture_feed)", "an evaluation graph (engine.capture_feed_eval)")
+            raise ValueError(f"run_epoch_fed: train={train} takes {kinds[not train]}; `replay` is {kinds[train]}")
+        if probe:
+            raise ValueError("run_epoch_fed: a probing pass runs eagerly (replay=None)")
         if replay.feed is not feed:
             raise ValueError("run_epoch_fed: `replay` was captured on another feed")
+        if not train:
+            for name, mine in (("scores", table), ("rank", rank), ("record", record)):
+                if getattr(replay, name) is not mine:
+                    raise ValueError(f"run_epoch_fed: `replay` was captured with another {name} than this pass uses "
+                                     f"(capture_feed_eval(..., {name}=) against the pass's own: None where it has none)")
+    feed.start(order, muting=muting)
+    steps = replay.steps if replay is not None else 1
+    replays, singles, tail = feed_plan(n, B, steps, drop_last)
+    if train:
         for _ in range(replays):
             replay()
         slots = replay.slots[0]
         for _ in range(singles):
             feed.gather_into(slots)
             engine.train_step(*slots)
+            feed.accumulate(engine, slots[-1])
+    elif replay is not None:
+        for _ in range(replays):
+            replay()
+        slots = replay.slots[0]
+        for _ in range(singles):
+            feed.gather_into(slots)
+            engine.evaluate(*slots, **extra)
             feed.accumulate(engine, slots[-1])
     else:
         slots = feed.new_slots()

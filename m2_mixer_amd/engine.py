@@ -29,8 +29,11 @@ What changes relative to the module path (modules/mixer.py + torch autograd):
     keys are never written (the unimodal models of Gradient-Blending); clone() and probe() are the other two pieces
     gradblend.GradBlend is built from.  Either stage is one Stage record held by the engine family and
     one pair of hooks per engine class (_stage_options, _stage_packs).
+  * evaluate(..., record=): the evaluation step also appends its logits, predictions and labels to a prediction record on the
+    device (PredictionRecord, csrc/record.hip: the reference's test_preds.pt, read back once); capture_feed_eval() captures whole
+    evaluation steps that feed themselves, as capture_feed() captures training steps.
 This file is the engines: the step, the stages, the optimizer, capture.  The device-side accumulators (ScoreTable, RankBuffer,
-EpochFeed) live in accumulators.py, the parameter-layout functions in layout.py; every name stays importable from here.
+PredictionRecord, EpochFeed) live in accumulators.py, the parameter-layout functions in layout.py; every name stays importable from here.
 """
 from __future__ import annotations
 
@@ -46,7 +49,7 @@ import torch
 from . import _lib as L
 from . import config
 # this module stays the import surface: the accumulators and the layout functions are re-exported under their old names
-from .accumulators import EpochFeed, RankBuffer, ScoreTable  # noqa: F401
+from .accumulators import EpochFeed, PredictionRecord, RankBuffer, ScoreTable  # noqa: F401
 from .layout import (ENGINE_FUSIONS, _head_shapes, _is_layer_norm, _num_patch, _tower_shapes,  # noqa: F401
                      avmnist_param_shapes, frozen_key_prefixes, fusion_function_name, fusion_tokens, mimic_param_shapes,
                      trainable_flat_ranges, two_tower_param_shapes)
@@ -668,16 +671,44 @@ class _FlatEngine:
             self.rank.add(self.logits, truth)
 
     @torch.no_grad()
-    def evaluate(self, *batch, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None):
+    def evaluate(self, *batch, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None,
+                 record: Optional[PredictionRecord] = None):
         """validation/test step on `batch` (the inputs, then the labels): dropout off (the reference's shared_step under
         model.eval()).  scores: a table (new_score_table / score_table(split)) this batch's counts are added into.  rank: a
-        ranking buffer (new_rank_buffer / rank_buffer(split)) this batch's softmax rows are appended to."""
+        ranking buffer (new_rank_buffer / rank_buffer(split)) this batch's softmax rows are appended to.  record: a prediction
+        record (new_prediction_record / prediction_record(split)) this batch's logits, predictions and labels are appended to,
+        behind the launch that writes them."""
         self._forward(*batch, False, False)
         if scores is not None:
             scores.add(self.preds, batch[-1])
         if rank is not None:
             rank.add(self.logits, batch[-1])
+        if record is not None:
+            record.add(self, batch[-1])
         return self._eval_outputs()                  # views of `logits` / `losses` / `preds` under the reference's names
+
+    # ---- prediction records ----------------------------------------------------------------------------------
+    def new_prediction_record(self, capacity: int) -> PredictionRecord:
+        """An empty prediction record of `capacity` rows for this model's heads (one per split: evaluate(..., record=record)
+        appends to the one given)."""
+        return PredictionRecord(self.SCORES_TASK, self.HEAD_NAMES, self.K, capacity, self.device,
+                                uncertainty=getattr(self, "uncertainty", None) is not None)
+
+    def prediction_record(self, split: str, capacity: Optional[int] = None) -> PredictionRecord:
+        """The record of `split`, kept on the engine as its tables and ranking buffers are: made with `capacity` rows on first use
+        (which must give one); a later call may leave the capacity out, and one that names another capacity is refused (captured
+        graphs keep the first one's pointers).  Training steps keep no record: "train" is refused (evaluate the training split
+        under another name)."""
+        def new():
+            if capacity is None:
+                raise RuntimeError(f"prediction_record({split!r}): the first use must give the capacity in rows")
+            return self.new_prediction_record(capacity)
+
+        rec = self._of_split(split, None, "_split_records", new,
+                             "prediction_record('train'): training steps keep no record (evaluate the split under another name)")
+        if capacity is not None and int(capacity) != rec.capacity:
+            raise RuntimeError(f"prediction_record({split!r}, {capacity}): the record of this split holds {rec.capacity} rows")
+        return rec
 
     # ---- ranking buffers -------------------------------------------------------------------------------------
     def new_rank_buffer(self) -> RankBuffer:
@@ -951,6 +982,63 @@ class _FlatEngine:
             return out_losses
 
         replay.losses, replay.slots, replay.steps, replay.feed = out_losses, slots, steps, feed
+        if steps > 1:
+            replay.logits, replay.preds = outs[1], outs[2]
+        return replay
+
+    def capture_feed_eval(self, feed: EpochFeed, steps: int = 1, scores: Optional[ScoreTable] = None,
+                          rank: Optional[RankBuffer] = None, record: Optional[PredictionRecord] = None, grad_sync=None):
+        """capture_feed's evaluation counterpart: capture `steps` consecutive EVALUATION steps that feed themselves from `feed`;
+        returns a callable replay() without arguments.  Each captured step is: m2m_feed_gather into that step's input slots,
+        evaluate() on the slots (dropout off) with its count-table launch, ranking append and record append where `scores`,
+        `rank`, `record` are given, m2m_epoch_accumulate into the feed's accumulators -- so a validation or test pass is
+        n / (B * steps) replays, one feed.read() and, with a record, one record.read().  On a training engine or on
+        sibling(B, trains=False).  replay.slots / .steps / .feed / .losses as for capture_feed; replay.eval is True and
+        replay.scores / .rank / .record are the accumulators the graph adds into (data.run_epoch_fed checks them against the
+        pass's own).
+        Like capture() it leaves everything as it found it: the warm-up runs outside the capture and is undone -- the feed's cursor
+        and accumulators, the table, the ranking state and the record's state included; parameters, Adam moments and the step and
+        dropout counters are not touched by an evaluation in the first place.  Captured training graphs stay valid.
+        A bf16 engine whose weights changed since its last pack() -- an evaluating sibling after training steps on its parent --
+        must be packed before a replay, as before any evaluation on a sibling; the graph does not hide a pack().
+        Single GPU only: a grad_sync is refused, as in capture_feed."""
+        if grad_sync is not None:
+            raise ValueError("capture_feed_eval is only supported without a gradient exchange (single GPU)")
+        if steps < 1:
+            raise ValueError("capture_feed_eval: steps >= 1")
+        if feed.B != self.B or feed.device != self.device:
+            raise ValueError(f"capture_feed_eval: the feed's batch size / device ({feed.B}, {feed.device}) are not the engine's "
+                             f"({self.B}, {self.device})")
+        feed.bind(self)
+        slots = [feed.new_slots() for _ in range(steps)]
+
+        def fed_step(i):
+            feed.gather_into(slots[i])
+            self.evaluate(*slots[i], scores=scores, rank=rank, record=record)
+            feed.accumulate(self, slots[i][-1])
+
+        touched = [feed.state, feed._acc]
+        if feed.mute_state is not None:
+            touched.append(feed.mute_state)              # (the warm-up gathers advance the muting schedule's step index too)
+        for acc, attr in ((scores, "table"), (rank, "state"), (record, "state")):
+            if acc is not None:
+                touched.append(getattr(acc, attr))
+        self._undo_warmup(lambda: fed_step(0), touched)
+        with self._per_step_outputs(steps) as (outs, enter):
+            def all_steps():
+                for i in range(steps):
+                    enter(i)
+                    fed_step(i)
+
+            g = self._graph_of(all_steps)
+        out_losses = self.losses if outs is None else outs[0]
+
+        def replay():
+            g.replay()
+            return out_losses
+
+        replay.losses, replay.slots, replay.steps, replay.feed, replay.eval = out_losses, slots, steps, feed, True
+        replay.scores, replay.rank, replay.record = scores, rank, record
         if steps > 1:
             replay.logits, replay.preds = outs[1], outs[2]
         return replay
@@ -1484,11 +1572,13 @@ class AVMnistUQEngine(AVMnistEngine):
         return True                                           # m2m_heads_edl keeps m2m_heads_ce's g_part contract
 
     @torch.no_grad()
-    def evaluate(self, *batch, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None):
-        """AVMnistEngine.evaluate; `preds` is the combined prediction, and the three uncertainties (B) are returned as well."""
+    def evaluate(self, *batch, scores: Optional[ScoreTable] = None, rank: Optional[RankBuffer] = None,
+                 record: Optional[PredictionRecord] = None):
+        """AVMnistEngine.evaluate; `preds` is the combined prediction, and the three uncertainties (B) are returned as well (a
+        record of this engine holds them per sample)."""
         if rank is not None:
             raise RuntimeError("AVMnistUQEngine: ranking buffers are not built for the evidential model")
-        return super().evaluate(*batch, scores=scores)
+        return super().evaluate(*batch, scores=scores, record=record)
 
     def _eval_outputs(self) -> dict:
         out = super()._eval_outputs()

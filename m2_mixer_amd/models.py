@@ -179,6 +179,7 @@ class _MultiLossModule(nn.Module):
         self.dropout = self.model_cfg.get("dropout", 0.0)
         self._engine = None                          # bind_engine: the fused engine whose buffers hold this module's parameters
         self._two_stage = False                      # bind_engine(..., two_stage=True): the bound engine follows the freeze epoch
+        self._test_record = False                    # bind_engine(..., test_record=True): test_step appends to the engine's "test" record
         self._engine_optimizer: Optional[EngineOptimizer] = None     # the latest configure_optimizers() of a bound module
 
     #: the heads in the order of the reference's `gb_weights` list (None: the task has no Gradient-Blending)
@@ -293,9 +294,11 @@ class _MultiLossModule(nn.Module):
         self.checkpoint_path = str(path)
         return str(path)
 
-    def save_test_preds(self, outputs: Sequence[Dict[str, torch.Tensor]], save_dir: Optional[str] = None) -> str:
+    def save_test_preds(self, outputs: Optional[Sequence[Dict[str, torch.Tensor]]] = None, save_dir: Optional[str] = None) -> str:
         """test_epoch_end's dump (models/avmnist.py:382-398): the listed shared_step outputs of every test batch,
-        concatenated, as `test_preds.pt` next to the checkpoint."""
+        concatenated, as `test_preds.pt` next to the checkpoint.  outputs=None (a module bound with test_record=True): the same
+        file from the engine's "test" prediction record, which every test_step appended to on the device -- read back once, then
+        emptied for the next test pass."""
         if save_dir is None:
             if self.checkpoint_path is None:
                 raise RuntimeError("save_test_preds: no checkpoint path to save next to; pass save_dir")
@@ -303,8 +306,19 @@ class _MultiLossModule(nn.Module):
         os.makedirs(save_dir or ".", exist_ok=True)
         if not self.TEST_PRED_KEYS:
             raise NotImplementedError(f"{type(self).__name__}: the reference dumps no test predictions for this task")
-        out = {k: torch.cat([o[k].detach().cpu() for o in outputs]) for k in self.TEST_PRED_KEYS}
         path = os.path.join(save_dir, "test_preds.pt")
+        if outputs is None:
+            if self._engine is None:
+                raise RuntimeError("save_test_preds: outputs=None reads a bound engine's test record; this module is not bound "
+                                   "(pass the list of test_step outputs)")
+            if not self._test_record:
+                raise RuntimeError("save_test_preds: outputs=None needs bind_engine(..., test_record=True); this module was bound "
+                                   "without the record (pass the list of test_step outputs)")
+            rec = self._engine.prediction_record("test")
+            rec.save(path, self.TEST_PRED_KEYS)
+            rec.reset()
+            return path
+        out = {k: torch.cat([o[k].detach().cpu() for o in outputs]) for k in self.TEST_PRED_KEYS}
         torch.save(out, path)
         return path
 
@@ -347,7 +361,7 @@ class _MultiLossModule(nn.Module):
         return self._engine
 
     def bind_engine(self, batch_size: int, precision: Optional[str] = None, scores: bool = False, rank_scores: bool = False,
-                    rank_capacity: int = 65536, two_stage: bool = False):
+                    rank_capacity: int = 65536, two_stage: bool = False, test_record: bool = False, record_capacity: int = 65536):
         """Engine-backed mode: build the fused engine (engine.py) for `batch_size`, copy this module's weights into it, then
         point every parameter's `.data` at the engine's buffer (`engine.params[key]`): the Parameter objects stay the same,
         `parameters()`, `state_dict()`, `save_checkpoint()` read the live weights, and no copy is taken again.  From then on
@@ -369,7 +383,11 @@ class _MultiLossModule(nn.Module):
         buffers on the device (engine.RankBuffer, `rank_capacity` rows each: a split must fit), and the three epoch-end hooks
         return the ranking scores as well (scores.RANK_SCORES: MIMIC's `auroc`, the reference's name for macro average
         precision, models/mimic.py:162-180; AV-MNIST `ap_macro`, `roc_auc_macro`) -- merged with the count-table scores, or on
-        their own with scores=False.  Off (the default): no buffer, no launch."""
+        their own with scores=False.  Off (the default): no buffer, no launch.
+        test_record=True: test_step also appends its batch's logits, predictions and labels to the engine's "test" prediction
+        record on the device (engine.PredictionRecord, `record_capacity` rows: the test split must fit; every batch size shares
+        the one record), and save_test_preds() without a list writes test_preds.pt from it.  Off (the default): no record, no
+        launch."""
         if self._engine is not None:
             raise RuntimeError("bind_engine: this module is already bound to an engine")
         if not two_stage:
@@ -389,6 +407,9 @@ class _MultiLossModule(nn.Module):
         self._bind_buffers(eng)
         self._engine = eng
         self._two_stage = bool(two_stage)
+        self._test_record = bool(test_record)
+        if self._test_record:
+            eng.prediction_record("test", record_capacity)
         if self._two_stage and self.modalities_freezed:
             eng.freeze_modalities()
         self._replay = None
@@ -518,6 +539,8 @@ class _MultiLossModule(nn.Module):
         extra = {} if table is None else {"scores": table}
         if rank is not None:
             extra["rank"] = rank
+        if mode == "test" and self._test_record:
+            extra["record"] = self._engine.prediction_record("test")
         sib.evaluate(xa.contiguous(), xb.contiguous(), labels.contiguous(), **extra)
         return self._engine_eval_outputs(sib, batch, labels)
 
