@@ -2,6 +2,7 @@
   ScoreTable   integer count table of one split (csrc/scores.hip)      -> accuracy / precision / recall / F1 (scores.py)
   RankBuffer   softmax rows and labels of one split (csrc/rank.hip)    -> average precision / ROC-AUC (scores.py)
   PredictionRecord  logits, predictions and labels of one split, row by row (csrc/record.hip) -> the reference's test_preds.pt
+  PassAccumulators  the three above as one pass over a split uses them (pass_accumulators picks them)
   EpochFeed    one split's resident tensors behind a device-side order and cursor, with the epoch's loss sums and hit counts
                (csrc/feed.hip); engine.capture_feed captures steps that feed themselves from it
 Of an engine they use `losses`, `logits`, `preds`, `uncertainty` and `B` only: this module imports the library (_lib) and scores,
@@ -9,7 +10,7 @@ never engine, which re-exports the classes.
 """
 from __future__ import annotations
 
-from typing import Dict, Optional, Sequence, Tuple
+from typing import Dict, List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -243,6 +244,44 @@ class PredictionRecord:
         got = self.read()
         torch.save({k: got[k].clone() for k in (self.save_keys if keys is None else keys)}, path)
         return path
+
+
+class PassAccumulators(NamedTuple):
+    """What one pass over a split adds into beside its losses: the count table, the ranking buffer and the prediction record,
+    each None where the pass has none.  The one place that knows how the three are reset, handed to evaluate(), read and put
+    back after a warm-up."""
+
+    scores: Optional[ScoreTable] = None
+    rank: Optional[RankBuffer] = None
+    record: Optional[PredictionRecord] = None
+
+    def kwargs(self) -> Dict[str, object]:
+        """evaluate(**kwargs()): the members present, under evaluate's names (none: {} -- an evaluate without keywords serves)."""
+        return {k: a for k, a in zip(self._fields, self) if a is not None}
+
+    def reset(self):
+        for a in self.kwargs().values():
+            a.reset()
+
+    def compute(self) -> Dict[str, float]:
+        """The table's numbers, then the ranking buffer's merged over them (the record is read by its owner: read() / save())."""
+        out = {} if self.scores is None else self.scores.compute()
+        if self.rank is not None:
+            out.update(self.rank.compute())
+        return out
+
+    def state(self) -> List[torch.Tensor]:
+        """The tensors a warm-up step changes and must put back: the table's counts, the two cursors (rows behind a cursor are dead)."""
+        return [getattr(a, attr) for a, attr in zip(self, ("table", "state", "state")) if a is not None]
+
+
+def pass_accumulators(engine, split: str, train: bool = False, record: Optional[PredictionRecord] = None) -> PassAccumulators:
+    """The accumulators of a pass over `split` on `engine` (anything run_epoch drives: an engine without `scores` / `rank` has
+    none).  A training pass counts into the training table and buffer (the captured step adds there), an evaluating pass into
+    `split`'s own -- the training split's under "train_eval"."""
+    which = "train" if train else (split if split != "train" else "train_eval")
+    return PassAccumulators(engine.score_table(which) if getattr(engine, "scores", None) is not None else None,
+                            engine.rank_buffer(which) if getattr(engine, "rank", None) is not None else None, record)
 
 
 class EpochFeed:

@@ -10,10 +10,13 @@ memory and reach the host once per `log_interval_steps`, so the captured graph i
 from __future__ import annotations
 
 import os
-from typing import Dict, Iterator, Optional, Tuple
+from contextlib import contextmanager, nullcontext
+from typing import Dict, Iterator, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
+
+from .accumulators import pass_accumulators
 
 
 class ResidentAVMnist:
@@ -133,15 +136,61 @@ class PlateauLR:
         return self.lr
 
 
+def tail_engine_for(engine, rows: int, trains: bool = True, given=None, reuse: Optional[bool] = None, keep: Optional[dict] = None):
+    """The engine that takes a batch of `rows` rows beside `engine` (the ragged last batch of a split): `given` if there is one,
+    else the kept training sibling of that size (engine._tail_engines), else a new engine.sibling(rows, trains=trains) -- kept
+    there only if it trains: an evaluating sibling is never kept as the training one.
+    reuse: whether the kept training sibling may serve (default: a training step only; run_epoch also evaluates on it).
+    keep: a dict of the caller's in which an EVALUATING sibling is found and kept (GradBlend's probing passes)."""
+    if given is not None:
+        return given
+    found = engine._tail_engines.get(rows) if (trains if reuse is None else reuse) else None
+    if found is None and not trains and keep is not None:
+        found = keep.get(rows)
+    if found is None:
+        found = engine.sibling(rows, trains=trains)
+        if trains:
+            engine._tail_engines[rows] = found
+        elif keep is not None:
+            keep[rows] = found
+    return found
+
+
+@contextmanager
+def tail_step(engine, tail, trains: bool):
+    """Around one step of `tail` (tail_engine_for) on weights it shares with `engine`: its packed operand copies missed every step
+    since its last use -- pack() before; a training step changed the weights under the parent's copies -- engine.pack() after."""
+    tail.pack()
+    yield tail
+    if trains:
+        engine.pack()
+
+
 def prepare_tail_engine(engine, data: "ResidentAVMnist", split: str, batch_size: int):
     """The training engine of `split`'s ragged last batch, built NOW (before engine.capture()) and kept on the engine for
     run_epoch; None when the split divides evenly."""
     rem = data.num_samples(split) % batch_size
-    if rem == 0:
-        return None
-    if rem not in engine._tail_engines:
-        engine._tail_engines[rem] = engine.sibling(rem)
-    return engine._tail_engines[rem]
+    return tail_engine_for(engine, rem) if rem else None
+
+
+def epoch_metrics(heads: Sequence[str], loss_sums, weighted_loss, steps: int, samples: int, hits=None, unc=None) -> Dict[str, float]:
+    """The metrics dict of one pass (run_epoch's docstring names the keys).  heads: the two modality names; loss_sums: the step
+    losses [a, b, fusion, total] summed over the steps; weighted_loss: the total weighted by each step's batch size; hits:
+    [a, b, fusion] correct predictions, or None (multilabel predictions have no hit count); unc: [a, b, fusion] sums of the
+    steps' batch-mean uncertainties, or None."""
+    a, b = heads
+    ds, dn = max(steps, 1), max(samples, 1)
+    out = {"loss": float(weighted_loss) / dn, "loss_step_mean": float(loss_sums[3]) / ds, f"loss_{a}": float(loss_sums[0]) / ds,
+           f"loss_{b}": float(loss_sums[1]) / ds, "loss_fusion": float(loss_sums[2]) / ds, "steps": steps, "samples": samples}
+    if hits is not None:
+        ha, hb, hf = (int(round(float(h))) for h in hits)
+        out.update({"acc": float(hits[2]) / dn, f"acc_{a}": float(hits[0]) / dn, f"acc_{b}": float(hits[1]) / dn,
+                    "hits": hf, f"hits_{a}": ha, f"hits_{b}": hb})
+    if unc is not None:
+        # the mean over the steps of each step's batch mean, the ragged tail as one step (models/avmnist.py:556-572); the plain
+        # name is the fusion head's
+        out.update({"uncertainty": float(unc[2]) / ds, f"uncertainty_{a}": float(unc[0]) / ds, f"uncertainty_{b}": float(unc[1]) / ds})
+    return out
 
 
 def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train: bool, log_interval_steps: int = 50,
@@ -176,19 +225,8 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
     here at the start, counted once at the end) and the ranking scores are added under their own names (`ap_macro`,
     `roc_auc_macro`, `ap_macro_image`, ...: scores.RANK_SCORES); the split must fit the engine's rank_capacity."""
     dev = engine.device
-    table = None
-    if getattr(engine, "scores", None) is not None:
-        # a training pass counts into the training table (the captured step adds there); an evaluating pass into `split`'s own
-        table = engine.score_table("train" if train else (split if split != "train" else "train_eval"))
-    if table is not None:
-        table.reset()
-    rank = None
-    if getattr(engine, "rank", None) is not None:                  # rank_scores=True: the pass's ranking buffer, the same way
-        rank = engine.rank_buffer("train" if train else (split if split != "train" else "train_eval"))
-        rank.reset()
-    extra = {} if table is None else {"scores": table}
-    if rank is not None:
-        extra["rank"] = rank
+    accs = pass_accumulators(engine, split, train)
+    accs.reset()
     # [loss_a, loss_b, loss_fusion, loss] step sums | the same weighted by the step's batch size | hits a, b, fusion
     acc = torch.zeros(11, device=dev, dtype=torch.float64)
     seen, host = 0, np.zeros(11)
@@ -199,28 +237,24 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
     if shuffle and getattr(data, "world", 1) > 1:
         gen = torch.Generator(device=data.device)
         gen.manual_seed(int(shuffle_seed) + int(epoch))
+
+    def step(eng, *batch):
+        if not train:
+            eng.evaluate(*batch, **accs.kwargs())
+        elif replay is not None and eng is engine:
+            replay(*batch)
+        else:
+            eng.train_step(*batch, grad_sync=grad_sync)
+
     for i, (image, audio, labels) in enumerate(data.batches(split, batch_size, shuffle=shuffle, generator=gen)):
         bs = labels.shape[0]
         eng = engine
-        if bs != batch_size:                                       # the ragged last batch
-            if tail_engine is None:
-                tail_engine = engine._tail_engines.get(bs)
-            if tail_engine is None:
-                tail_engine = engine.sibling(bs, trains=train)
-                if train:                                          # (an evaluating sibling is not kept as the training one)
-                    engine._tail_engines[bs] = tail_engine
-            eng = tail_engine
-            eng.pack()                                             # its packed copies missed every step since its last use
-            image, audio, labels = image.contiguous(), audio.contiguous(), labels.contiguous()
-        if train:
-            if replay is not None and eng is engine:
-                replay(image, audio, labels)
-            else:
-                eng.train_step(image, audio, labels, grad_sync=grad_sync)
-        else:
-            eng.evaluate(image, audio, labels, **extra)
-        if eng is not engine and train:
-            engine.pack()                                          # the tail step changed the weights
+        if bs == batch_size:
+            step(engine, image, audio, labels)
+        else:                                                      # the ragged last batch (a kept training sibling evaluates too)
+            eng = tail_engine_for(engine, bs, train, tail_engine, reuse=True)
+            with tail_step(engine, eng, train):
+                step(eng, image.contiguous(), audio.contiguous(), labels.contiguous())
         acc[:4] += eng.losses                                      # device-side: no host round trip
         acc[4:8] += eng.losses * bs
         acc[8:11] += (eng.preds == labels.to(eng.preds.dtype)[None, :]).sum(dim=1)
@@ -229,16 +263,8 @@ def run_epoch(engine, data: ResidentAVMnist, split: str, batch_size: int, train:
             host = acc.cpu().numpy()                               # the only sync of the interval
             if log is not None:
                 log({"split": split, "step": i + 1, "loss": host[3] / (i + 1), "acc": host[10] / seen})
-    steps, n = max(nb, 1), max(seen, 1)
-    a, b = getattr(engine, "MODS", ("image", "audio"))
-    out = {} if table is None else table.compute()
-    if rank is not None:
-        out.update(rank.compute())
-    out.update({"loss": float(host[7]) / n, "loss_step_mean": float(host[3]) / steps,
-            f"loss_{a}": float(host[0]) / steps, f"loss_{b}": float(host[1]) / steps, "loss_fusion": float(host[2]) / steps,
-            "acc": float(host[10]) / n, f"acc_{a}": float(host[8]) / n, f"acc_{b}": float(host[9]) / n,
-            "hits": int(round(host[10])), f"hits_{a}": int(round(host[8])), f"hits_{b}": int(round(host[9])),
-            "steps": nb, "samples": seen})
+    out = accs.compute()
+    out.update(epoch_metrics(getattr(engine, "MODS", ("image", "audio")), host[:4], host[7], nb, seen, hits=host[8:11]))
     return out
 
 
@@ -287,19 +313,9 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
         raise ValueError(f"run_epoch_fed: n = {n} samples of a split of {feed.n}")
     if B != engine.B:
         raise ValueError(f"run_epoch_fed: the feed's batch size {B} is not the engine's {engine.B}")
-    which = "train" if train else (split if split != "train" else "train_eval")
-    table = engine.score_table(which) if getattr(engine, "scores", None) is not None else None
-    rank = engine.rank_buffer(which) if getattr(engine, "rank", None) is not None else None
+    accs = pass_accumulators(engine, split, train, record)
     if record is not None and (train or probe):
         raise ValueError("run_epoch_fed: record= goes with an evaluating pass (train=False, probe=False)")
-    for t in (table, rank, record):
-        if t is not None:
-            t.reset()
-    extra = {} if table is None else {"scores": table}
-    if rank is not None:
-        extra["rank"] = rank
-    if record is not None:
-        extra["record"] = record
     feed.bind(engine)
     if muting is not None and not train:
         raise ValueError("run_epoch_fed: evaluation never mutes (muting= goes with train=True)")
@@ -314,56 +330,33 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
         if replay.feed is not feed:
             raise ValueError("run_epoch_fed: `replay` was captured on another feed")
         if not train:
-            for name, mine in (("scores", table), ("rank", rank), ("record", record)):
+            for name, mine in accs._asdict().items():
                 if getattr(replay, name) is not mine:
                     raise ValueError(f"run_epoch_fed: `replay` was captured with another {name} than this pass uses "
                                      f"(capture_feed_eval(..., {name}=) against the pass's own: None where it has none)")
+    accs.reset()
     feed.start(order, muting=muting)
-    steps = replay.steps if replay is not None else 1
-    replays, singles, tail = feed_plan(n, B, steps, drop_last)
-    if train:
-        for _ in range(replays):
-            replay()
-        slots = replay.slots[0]
-        for _ in range(singles):
+    # one step, whatever the pass: the graph's replays, the full batches that fill none on its first slots, the ragged tail
+    kind = "train_step" if train else ("probe" if probe else "evaluate")
+    kwargs = accs.kwargs() if kind == "evaluate" else {}
+
+    def fed_step(eng, slots, around=nullcontext()):
+        with around:
             feed.gather_into(slots)
-            engine.train_step(*slots)
-            feed.accumulate(engine, slots[-1])
-    elif replay is not None:
-        for _ in range(replays):
-            replay()
-        slots = replay.slots[0]
-        for _ in range(singles):
-            feed.gather_into(slots)
-            engine.evaluate(*slots, **extra)
-            feed.accumulate(engine, slots[-1])
-    else:
-        slots = feed.new_slots()
-        for _ in range(replays * steps + singles):
-            feed.gather_into(slots)
-            if probe:
-                engine.probe(*slots)
-            else:
-                engine.evaluate(*slots, **extra)
-            feed.accumulate(engine, slots[-1])
+            getattr(eng, kind)(*slots, **kwargs)
+        feed.accumulate(eng, slots[-1])
+
+    replays, singles, tail = feed_plan(n, B, replay.steps if replay is not None else 1, drop_last)
+    if replay is None:
+        replays, singles = 0, replays                              # (a graph of one step: every full batch is a single step)
+    for _ in range(replays):
+        replay()
+    slots = replay.slots[0] if replay is not None else feed.new_slots()
+    for _ in range(singles):
+        fed_step(engine, slots)
     if tail:
-        if tail_engine is None:
-            tail_engine = engine._tail_engines.get(tail) if train else None
-        if tail_engine is None:
-            tail_engine = engine.sibling(tail, trains=train)
-            if train:
-                engine._tail_engines[tail] = tail_engine
-        tslots = feed.new_slots(tail)
-        tail_engine.pack()                                         # its packed copies missed every step since its last use
-        feed.gather_into(tslots)
-        if train:
-            tail_engine.train_step(*tslots)
-            engine.pack()                                          # the tail step changed the weights
-        elif probe:
-            tail_engine.probe(*tslots)
-        else:
-            tail_engine.evaluate(*tslots, **extra)
-        feed.accumulate(tail_engine, tslots[-1])
+        sib = tail_engine_for(engine, tail, train, tail_engine)
+        fed_step(sib, feed.new_slots(tail), tail_step(engine, sib, train))
     unc = None
     if feed.nunc:
         sums, counts, unc = feed.read(with_uncertainty=True)       # the only sync of the epoch
@@ -371,20 +364,8 @@ def run_epoch_fed(engine, feed, replay, n: Optional[int] = None, train: bool = T
         sums, counts = feed.read()
     feed.check()
     nl, nh = feed.nloss, feed.nheads
-    nsteps, seen = int(counts[nh]), int(counts[nh + 1])
-    a, b = engine.HEAD_NAMES[:2]                                    # (image, audio) / (image, text) / (static, time)
-    out = {} if table is None else table.compute()
-    if rank is not None:
-        out.update(rank.compute())
-    ds, dn = max(nsteps, 1), max(seen, 1)
-    out.update({"loss": float(sums[nl + 3]) / dn, "loss_step_mean": float(sums[3]) / ds,
-                f"loss_{a}": float(sums[0]) / ds, f"loss_{b}": float(sums[1]) / ds, "loss_fusion": float(sums[2]) / ds,
-                "steps": nsteps, "samples": seen})
-    if nh == 3:
-        out.update({"acc": int(counts[2]) / dn, f"acc_{a}": int(counts[0]) / dn, f"acc_{b}": int(counts[1]) / dn,
-                    "hits": int(counts[2]), f"hits_{a}": int(counts[0]), f"hits_{b}": int(counts[1])})
-    if unc is not None:
-        # the mean over the steps of each step's batch mean, the ragged tail as one step (models/avmnist.py:556-572); rows are
-        # the engine's [a, b, fusion], the plain name is the fusion head's
-        out.update({"uncertainty": float(unc[2]) / ds, f"uncertainty_{a}": float(unc[0]) / ds, f"uncertainty_{b}": float(unc[1]) / ds})
+    out = accs.compute()
+    # heads: (image, audio) / (image, text) / (static, time); multilabel predictions have no hit count (nh == 0)
+    out.update(epoch_metrics(engine.HEAD_NAMES[:2], sums[:4], sums[nl + 3], int(counts[nh]), int(counts[nh + 1]),
+                             hits=counts[:3] if nh == 3 else None, unc=unc))
     return out

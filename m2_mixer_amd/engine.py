@@ -49,7 +49,7 @@ import torch
 from . import _lib as L
 from . import config
 # this module stays the import surface: the accumulators and the layout functions are re-exported under their old names
-from .accumulators import EpochFeed, PredictionRecord, RankBuffer, ScoreTable  # noqa: F401
+from .accumulators import EpochFeed, PassAccumulators, PredictionRecord, RankBuffer, ScoreTable  # noqa: F401
 from .layout import (ENGINE_FUSIONS, _head_shapes, _is_layer_norm, _num_patch, _tower_shapes,  # noqa: F401
                      avmnist_param_shapes, frozen_key_prefixes, fusion_function_name, fusion_tokens, mimic_param_shapes,
                      trainable_flat_ranges, two_tower_param_shapes)
@@ -891,11 +891,9 @@ class _FlatEngine:
         REAL training steps (lazy initialisation of the launches -- LDS attributes, allocations -- must happen outside the
         capture); everything they change is restored afterwards, so a capture leaves the model exactly as it found it.
         extra_state: the tensors a caller's step changes beyond the engine's own (a feed's cursor and accumulators)."""
-        state = [self.flat_p, self.flat_m, self.flat_v, self.flat_g, self.adam_state, self.drop_step, *extra_state]
-        if self.scores is not None:
-            state.append(self.scores.table)          # (the warm-up steps count their batch too)
-        if self.rank is not None:
-            state.append(self.rank.state)            # (... and append it: the cursor goes back, the rows behind it are dead)
+        # (the warm-up steps count and append their batch too: the training table and the ranking cursor go back)
+        state = [self.flat_p, self.flat_m, self.flat_v, self.flat_g, self.adam_state, self.drop_step, *extra_state,
+                 *PassAccumulators(self.scores, self.rank).state()]
         snap = [t.clone() for t in state]
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream())
@@ -949,23 +947,33 @@ class _FlatEngine:
         Single GPU only: a grad_sync is refused (every rank would need its shard of the order)."""
         if grad_sync is not None:
             raise ValueError("capture_feed is only supported without a gradient exchange (single GPU)")
-        if steps < 1:
-            raise ValueError("capture_feed: steps >= 1")
-        if feed.B != self.B or feed.device != self.device:
-            raise ValueError(f"capture_feed: the feed's batch size / device ({feed.B}, {feed.device}) are not the engine's "
-                             f"({self.B}, {self.device})")
         self._check_trains()
+        replay, graph = self._capture_fed("capture_feed", feed, steps, self.fused_step, [], {})
+        self._slots_folded = False
+        self._graph = (graph,)
+        return replay
+
+    def _capture_fed(self, name: str, feed: EpochFeed, steps: int, step, restore: Sequence[torch.Tensor], attrs: dict):
+        """The scaffold capture_feed and capture_feed_eval share: `steps` times gather into the step's slots, step(*slots), accumulate
+        -- warmed up outside the capture and undone (the feed's cursor, accumulators and muting step index, and `restore`: what
+        step() changes beyond the engine's own state), captured as one graph.  Returns (replay, the graph): replay() with the
+        attributes both forms have (losses, slots, steps, feed; logits and preds of a multi-step graph) and `attrs`."""
+        if steps < 1:
+            raise ValueError(f"{name}: steps >= 1")
+        if feed.B != self.B or feed.device != self.device:
+            raise ValueError(f"{name}: the feed's batch size / device ({feed.B}, {feed.device}) are not the engine's "
+                             f"({self.B}, {self.device})")
         feed.bind(self)
         slots = [feed.new_slots() for _ in range(steps)]
 
         def fed_step(i):
             feed.gather_into(slots[i])
-            self.fused_step(*slots[i])
+            step(*slots[i])
             feed.accumulate(self, slots[i][-1])
 
         # (the warm-up gathers advance the muting schedule's step index too)
         mute = [] if feed.mute_state is None else [feed.mute_state]
-        self._undo_warmup(lambda: fed_step(0), [feed.state, feed._acc, *mute])
+        self._undo_warmup(lambda: fed_step(0), [feed.state, feed._acc, *mute, *restore])
         with self._per_step_outputs(steps) as (outs, enter):
             def all_steps():
                 for i in range(steps):
@@ -974,8 +982,6 @@ class _FlatEngine:
 
             g = self._graph_of(all_steps)
         out_losses = self.losses if outs is None else outs[0]
-        self._slots_folded = False
-        self._graph = (g,)
 
         def replay():
             g.replay()
@@ -984,7 +990,9 @@ class _FlatEngine:
         replay.losses, replay.slots, replay.steps, replay.feed = out_losses, slots, steps, feed
         if steps > 1:
             replay.logits, replay.preds = outs[1], outs[2]
-        return replay
+        for k, v in attrs.items():
+            setattr(replay, k, v)
+        return replay, g
 
     def capture_feed_eval(self, feed: EpochFeed, steps: int = 1, scores: Optional[ScoreTable] = None,
                           rank: Optional[RankBuffer] = None, record: Optional[PredictionRecord] = None, grad_sync=None):
@@ -1004,44 +1012,9 @@ class _FlatEngine:
         Single GPU only: a grad_sync is refused, as in capture_feed."""
         if grad_sync is not None:
             raise ValueError("capture_feed_eval is only supported without a gradient exchange (single GPU)")
-        if steps < 1:
-            raise ValueError("capture_feed_eval: steps >= 1")
-        if feed.B != self.B or feed.device != self.device:
-            raise ValueError(f"capture_feed_eval: the feed's batch size / device ({feed.B}, {feed.device}) are not the engine's "
-                             f"({self.B}, {self.device})")
-        feed.bind(self)
-        slots = [feed.new_slots() for _ in range(steps)]
-
-        def fed_step(i):
-            feed.gather_into(slots[i])
-            self.evaluate(*slots[i], scores=scores, rank=rank, record=record)
-            feed.accumulate(self, slots[i][-1])
-
-        touched = [feed.state, feed._acc]
-        if feed.mute_state is not None:
-            touched.append(feed.mute_state)              # (the warm-up gathers advance the muting schedule's step index too)
-        for acc, attr in ((scores, "table"), (rank, "state"), (record, "state")):
-            if acc is not None:
-                touched.append(getattr(acc, attr))
-        self._undo_warmup(lambda: fed_step(0), touched)
-        with self._per_step_outputs(steps) as (outs, enter):
-            def all_steps():
-                for i in range(steps):
-                    enter(i)
-                    fed_step(i)
-
-            g = self._graph_of(all_steps)
-        out_losses = self.losses if outs is None else outs[0]
-
-        def replay():
-            g.replay()
-            return out_losses
-
-        replay.losses, replay.slots, replay.steps, replay.feed, replay.eval = out_losses, slots, steps, feed, True
-        replay.scores, replay.rank, replay.record = scores, rank, record
-        if steps > 1:
-            replay.logits, replay.preds = outs[1], outs[2]
-        return replay
+        accs = PassAccumulators(scores, rank, record)
+        return self._capture_fed("capture_feed_eval", feed, steps, lambda *batch: self.evaluate(*batch, **accs.kwargs()),
+                                 accs.state(), dict(accs._asdict(), eval=True))[0]
 
 
 class _TwoTowerEngine(_FlatEngine):

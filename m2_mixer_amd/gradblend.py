@@ -87,23 +87,21 @@ class GradBlend:
         return c
 
     @staticmethod
-    def _probe_sums(eng, feed):
-        from .data import run_epoch_fed
-        tail, tail_engine = feed.n % eng.B, None
-        if tail:                                          # one evaluating sibling per tail size, kept for the later passes
-            tails = eng.__dict__.setdefault("_probe_tails", {})
-            tail_engine = tails.get(tail) or tails.setdefault(tail, eng.sibling(tail, trains=False))
-        run_epoch_fed(eng, feed, None, train=False, probe=True, tail_engine=tail_engine)
+    def _probe_sums(eng, feed, tails: dict):
+        """tails: the clone's evaluating siblings, one per tail size, kept for its later passes."""
+        from .data import run_epoch_fed, tail_engine_for
+        tail = feed.n % eng.B
+        run_epoch_fed(eng, feed, None, train=False, probe=True,
+                      tail_engine=tail_engine_for(eng, tail, trains=False, keep=tails) if tail else None)
         return [float(v) for v in feed.read()[0][:3]]
 
     def _train(self, eng, feed):
         """`epochs` passes over the train part: the captured fed step, the ragged tail through the kept training sibling (built
         before the capture: sibling()'s rule)."""
         import torch
-        from .data import run_epoch_fed
-        tail = feed.n % eng.B
-        if tail and tail not in eng._tail_engines:
-            eng._tail_engines[tail] = eng.sibling(tail)
+        from .data import run_epoch_fed, tail_engine_for
+        if feed.n % eng.B:
+            tail_engine_for(eng, feed.n % eng.B)
         replay = eng.capture_feed(feed, 1)
         gen = torch.Generator(device=eng.device)
         gen.manual_seed(self.seed)
@@ -120,20 +118,20 @@ class GradBlend:
         names = eng.HEAD_NAMES
         val, train = self._parts()
         dev, B = eng.device, eng.B
-        uni = self._clone()                               # clone A
+        uni, tails = self._clone(), {}                    # clone A
         feed_tr, feed_va = EpochFeed(train, B, dev), EpochFeed(val, B, dev)
         # before training: one probing pass of the unchanged weights gives all three heads' sums
-        n_tr, n_va = self._probe_sums(uni, feed_tr), self._probe_sums(uni, feed_va)
+        n_tr, n_va = self._probe_sums(uni, feed_tr, tails), self._probe_sums(uni, feed_va, tails)
         uni.train_modalities_only()
         self._train(uni, feed_tr)
-        u_tr, u_va = self._probe_sums(uni, feed_tr), self._probe_sums(uni, feed_va)
-        del uni
-        multi = self._clone()                             # clone B
+        u_tr, u_va = self._probe_sums(uni, feed_tr, tails), self._probe_sums(uni, feed_va, tails)
+        del uni, tails
+        multi, tails = self._clone(), {}                  # clone B
         multi.freeze_modalities()
         feed_tr, feed_va = EpochFeed(train, B, dev), EpochFeed(val, B, dev)
         self._train(multi, feed_tr)
-        m_tr, m_va = self._probe_sums(multi, feed_tr), self._probe_sums(multi, feed_va)
-        del multi
+        m_tr, m_va = self._probe_sums(multi, feed_tr, tails), self._probe_sums(multi, feed_va, tails)
+        del multi, tails
         after_tr, after_va = [u_tr[0], u_tr[1], m_tr[2]], [u_va[0], u_va[1], m_va[2]]
         self.sums = {h: dict(zip(SUM_KEYS, (n_tr[i], n_va[i], after_tr[i], after_va[i]))) for i, h in enumerate(names)}
         ws = normalise([blend_weight(*(self.sums[h][k] for k in SUM_KEYS)) for h in names])

@@ -29,6 +29,8 @@ import torch
 from torch import nn
 
 from . import modules
+from .accumulators import pass_accumulators
+from .data import tail_engine_for, tail_step
 
 
 class _LenientPickle:
@@ -413,7 +415,6 @@ class _MultiLossModule(nn.Module):
         if self._two_stage and self.modalities_freezed:
             eng.freeze_modalities()
         self._replay = None
-        self._train_siblings: Dict[int, Any] = {}
         self._eval_siblings: Dict[int, Any] = {}
         self._engine_version = 0                     # += 1 whenever the weights change (an engine step, a load_state_dict)
         self._hip_modules = [m for m in self.modules() if hasattr(m, "invalidate_packs")]
@@ -476,14 +477,13 @@ class _MultiLossModule(nn.Module):
                 "logits": lg[2]}
 
     def _train_sibling(self, bs: int):
-        sib = self._train_siblings.get(bs)
-        if sib is None:
-            if self._replay is not None:
-                # sibling() may narrow the gradient ranges the captured update leaves uncleared: capture again afterwards
-                self._replay = None
-                self._engine.release_capture()
-            sib = self._train_siblings[bs] = self._engine.sibling(bs)
-            self._link_sibling(sib)
+        eng = self._engine
+        if bs not in eng._tail_engines and self._replay is not None:
+            # sibling() may narrow the gradient ranges the captured update leaves uncleared: capture again afterwards
+            self._replay = None
+            eng.release_capture()
+        sib = tail_engine_for(eng, bs)               # (kept in engine._tail_engines, the one store of training tails)
+        self._link_sibling(sib)
         return sib
 
     def _eval_sibling(self, bs: int):
@@ -523,9 +523,8 @@ class _MultiLossModule(nn.Module):
             src = eng
         else:
             src = self._train_sibling(bs)
-            src.pack()                               # pack-before / pack-after (data.run_epoch)
-            src.train_step(xa.contiguous(), xb.contiguous(), labels.contiguous())
-            eng.pack()
+            with tail_step(eng, src, True):
+                src.train_step(xa.contiguous(), xb.contiguous(), labels.contiguous())
         self._engine_version += 1
         self._invalidate_module_packs()
         return self._engine_train_outputs(src, labels)
@@ -535,44 +534,21 @@ class _MultiLossModule(nn.Module):
             return self.shared_step(batch, mode=mode)
         xa, xb, labels = self._engine_batch(batch, train=False)
         sib = self._eval_sibling(labels.shape[0])
-        table, rank = self._score_table(mode), self._rank_buffer(mode)
-        extra = {} if table is None else {"scores": table}
-        if rank is not None:
-            extra["rank"] = rank
-        if mode == "test" and self._test_record:
-            extra["record"] = self._engine.prediction_record("test")
-        sib.evaluate(xa.contiguous(), xb.contiguous(), labels.contiguous(), **extra)
+        record = self._engine.prediction_record("test") if mode == "test" and self._test_record else None
+        accs = pass_accumulators(self._engine, mode, record=record)
+        sib.evaluate(xa.contiguous(), xb.contiguous(), labels.contiguous(), **accs.kwargs())
         return self._engine_eval_outputs(sib, batch, labels)
-
-    def _rank_buffer(self, split: str):
-        """The bound engine's ranking buffer of `split` ("train", "val", "test"); None when unbound or bound without
-        rank_scores."""
-        eng = self._engine
-        if eng is None or getattr(eng, "rank", None) is None:
-            return None
-        return eng.rank_buffer(split)
-
-    def _score_table(self, split: str):
-        """The bound engine's count table of `split` ("train", "val", "test"); None when unbound, bound without scores, or bound
-        to an engine that has none."""
-        eng = self._engine
-        if eng is None or getattr(eng, "scores", None) is None:
-            return None
-        return eng.score_table(split)
 
     def _epoch_scores(self, split: str) -> Optional[Dict[str, float]]:
         """compute() of `split`'s table under the reference's logging names (`<split>_<metric>`), then reset it -- what the
         torchmetrics objects do at an epoch end under Lightning.  One device-to-host copy."""
-        table, rank = self._score_table(split), self._rank_buffer(split)
-        if table is None and rank is None:
+        if self._engine is None:
             return None
-        out = {}
-        if table is not None:
-            out.update({f"{split}_{k}": v for k, v in table.compute().items()})
-            table.reset()
-        if rank is not None:                         # (bound with rank_scores=True: `<split>_auroc`, ... -- the buffer restarts empty)
-            out.update({f"{split}_{k}": v for k, v in rank.compute().items()})
-            rank.reset()
+        accs = pass_accumulators(self._engine, split, train=split == "train")      # ("train": the training steps' own)
+        if not accs.kwargs():
+            return None
+        out = {f"{split}_{k}": v for k, v in accs.compute().items()}
+        accs.reset()                                 # (the table and the ranking buffer restart empty)
         return out
 
     def training_epoch_end(self, outputs=None) -> Optional[Dict[str, float]]:

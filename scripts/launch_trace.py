@@ -3,7 +3,7 @@
 buffers the steps leave behind.  The tool a change of the Python host layer (engine.py, runtime.py) is verified with: two trees
 whose traces and hashes agree enqueue the same work with the same arguments.
 
-    python scripts/launch_trace.py --model avmnist_B --precision bf16 --batch 512 [--scenario base|stages|feed]
+    python scripts/launch_trace.py --model avmnist_B --precision bf16 --batch 512 [--scenario base|stages|feed|epochs]
                                    [--fusion SumFusion] [--out trace.txt] [--dump buffers.pt]
     PYTHONPATH=<another tree> M2M_LIB_PATH=<this tree's libm2mixer.so> python scripts/launch_trace.py ...    (the other side)
 
@@ -28,10 +28,18 @@ load_state_dict(seeded make_params):
           seeded rows, the tail's training sibling, capture_feed(steps=2), start(order), one replay, a fed step on the sibling,
           feed.read(), evaluate into the tables of "val"; then on a fresh engine freeze_modalities(), a feed with muting=True,
           start(order, muting=codes), capture_feed(steps=1), two replays.
+  epochs  whole passes through the drivers above the engine, on 5 * B + 3 seeded rows and an engine with scores=True (and
+          rank_scores=True): prepare_tail_engine, capture() + run_epoch(train=True, replay=), run_epoch(train=False) on "train" and
+          "val" (these three on the models with class predictions), capture_feed(steps=2) + run_epoch_fed(train=True),
+          capture_feed_eval(steps=2, scores=, rank=, record=) + run_epoch_fed(train=False, record=), run_epoch_fed(probe=True),
+          GradBlend(epochs=1).get_weights(), then a task module (tests/test_gpu_engine_backed.make_net) bound with scores=True,
+          test_record=True: training_step, validation_step and test_step at batch B and at batch 3.  The hash block adds the
+          splits' tables, ranking and record state, the record's rows, the returned metrics and GradBlend's twelve sums.
 A scenario's second engine (and a clone) has flat buffers of its own: from its construction on pointers are named after those
 (the clone's as clone.flat_p+<offset>).  The sha256 block holds, per engine of the scenario, the seven buffers of the base
 scenario (+ `uncertainty` on the evidential engine) and what the scenario adds: score tables, ranking state, the feed's state,
-accumulators and muting state.  stages and feed use names that exist since GradBlend (probe, clone, train_modalities_only).
+accumulators and muting state.  stages and feed use names that exist since GradBlend (probe, clone, train_modalities_only),
+epochs names that exist since capture_feed_eval and the prediction record.
 """
 import argparse
 import ctypes as C
@@ -422,7 +430,96 @@ def scenario_feed(rec, args):
     return bufs
 
 
-SCENARIOS = {"base": scenario_base, "stages": scenario_stages, "feed": scenario_feed}
+def scenario_epochs(rec, args):
+    """Whole passes over a split through every driver of the host layer (data.run_epoch / run_epoch_fed, gradblend.GradBlend, a
+    bound task module's step hooks) on n = 5 * B + 3 seeded rows: feed_plan(n, B, 2) is 2 replays, 1 single step and a tail of 3."""
+    from m2_mixer_amd import data as D
+    from m2_mixer_amd.gradblend import GradBlend
+    phase = lambda s: rec.emit("# " + s)
+    B, tail = args.batch, 3
+    n = 5 * B + tail
+    task = args.model.split("_")[0]
+    ranks = task != "mmimdb"                                     # (MM-IMDb refuses rank_scores=True ...
+    classes = task != "mmimdb"                                   # ... and run_epoch's hit counts take class predictions)
+    order = torch.randperm(n, generator=torch.Generator().manual_seed(args.seed + 3))
+    phase("construct")
+    eng, params, batch, rows = build(args, scores=True, rank_scores=ranks)
+    rec.set_flat(eng)
+    phase("load_state_dict")
+    eng.load_state_dict(params)
+
+    class Resident(D.ResidentTensors):                           # run_epoch iterates batches(); the tensors are any task's
+        batches = D.ResidentAVMnist.batches
+
+    data = Resident({"train": rows(n, args.seed + 2), "val": rows(n, args.seed + 4)})
+    phase("prepare_tail_engine")
+    D.prepare_tail_engine(eng, data, "train", B)
+    out = {}
+    if classes:
+        phase("capture")
+        replay = eng.capture(*batch)
+        phase("run_epoch(train=True, replay)")
+        out["run_epoch train"] = D.run_epoch(eng, data, "train", B, train=True, replay=replay)
+        for split in ("train", "val"):
+            phase(f"run_epoch(train=False) on {split!r}")
+            out[f"run_epoch eval {split}"] = D.run_epoch(eng, data, split, B, train=False)
+    phase("EpochFeed")
+    feed = E.EpochFeed(data.splits["train"], B, eng.device)
+    phase("capture_feed(steps=2)")
+    fed = eng.capture_feed(feed, steps=2)
+    phase("run_epoch_fed(train=True)")
+    out["fed train"] = D.run_epoch_fed(eng, feed, fed, train=True, order=order)
+    record = eng.prediction_record("val", n)
+    accs = {"scores": eng.score_table("val"), "rank": eng.rank_buffer("val") if ranks else None, "record": record}
+    phase("capture_feed_eval(steps=2, scores=, rank=, record=)")
+    fed_eval = eng.capture_feed_eval(feed, steps=2, **accs)
+    phase("run_epoch_fed(train=False, record=)")
+    out["fed eval"] = D.run_epoch_fed(eng, feed, fed_eval, train=False, split="val", record=record)
+    torch.cuda.synchronize()
+    bufs = engine_buffers(eng)
+    bufs.update(feed_buffers(eng, feed))
+    for split in ("train_eval", "val") if classes else ("val",):
+        bufs[f"scores_{split}"] = eng.score_table(split).table.cpu()
+        if ranks:
+            bufs[f"rank_{split}_state"] = eng.rank_buffer(split).state.cpu()
+    bufs["record_val_state"] = record.state.cpu()
+    bufs.update({"record_val_" + k: v for k, v in record.read().items()})
+    phase("run_epoch_fed(train=False, probe=True)")
+    out["fed probe"] = D.run_epoch_fed(eng, feed, None, train=False, probe=True, split="val")
+    bufs.update(feed_buffers(eng, feed, "probe."))
+    phase("GradBlend(epochs=1).get_weights")
+    gb = GradBlend(eng, data, epochs=1, seed=args.seed + 5)
+    gb.get_weights()
+    bufs["gradblend_sums"] = torch.tensor([[gb.sums[h][k] for k in sorted(gb.sums[h])] for h in eng.HEAD_NAMES], dtype=torch.float64)
+    for k, d in out.items():                                     # the returned metrics, as one float64 row per pass
+        bufs["metrics " + k] = torch.tensor([float(d[key]) for key in sorted(d)], dtype=torch.float64)
+        rec.emit(f"# keys {k}: {' '.join(sorted(d))}")
+
+    sys.path.append(os.path.join(ROOT, "tests"))
+    from test_gpu_engine_backed import make_net
+    rec.hold()
+    phase("module: make_net + bind_engine(scores=True, test_record=True)")
+    net, _ = make_net(task, eng.cfg, args.seed + 6, eng.device)
+    net.bind_engine(B, precision=args.precision, scores=True, rank_scores=ranks, test_record=True)
+    rec.set_flat(net.engine, "net.", keep=True)
+    names = {"avmnist": ("image", "audio", "label"), "mmimdb": ("image", "text", "label")}.get(task)
+    for nb in (B, tail):
+        mb = tuple(t[:nb].contiguous() for t in batch)
+        mb = mb if names is None else dict(zip(names, mb))
+        for hook in ("training_step", "validation_step", "test_step"):
+            phase(f"module {hook} at batch {nb}")
+            getattr(net, hook)(mb, 0)
+    torch.cuda.synchronize()
+    bufs.update(engine_buffers(net.engine, "net."))
+    for split in ("train", "val", "test"):
+        bufs[f"net.scores_{split}"] = net.engine.score_table(split).table.cpu()
+        if ranks:
+            bufs[f"net.rank_{split}_state"] = net.engine.rank_buffer(split).state.cpu()
+    bufs["net.record_test_state"] = net.engine.prediction_record("test").state.cpu()
+    return bufs
+
+
+SCENARIOS = {"base": scenario_base, "stages": scenario_stages, "feed": scenario_feed, "epochs": scenario_epochs}
 
 
 def main():
