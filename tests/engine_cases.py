@@ -11,8 +11,8 @@ Fields:
   name     test id
   engine   "avmnist" | "mmimdb" | "mimic"
   cfg      the complete config dict the engine is built from
-  B, p     batch size, dropout (0.5: the kernels' one-bit masks, any other p > 0: 16-bit draws); the MIMIC cases stay at p = 0
-           (the static MLP's masks have no export hook)
+  B, p     batch size, dropout (0.5: the kernels' one-bit masks, any other p > 0: 16-bit draws); the static MLP of a MIMIC case
+           has no mask probe: its masks come from the host replica of the dropout stream (engine_ref.mlp_masks)
   expect   decision -> value, or -> {"fp32": value, "bf16": value} where the precisions differ (the weight-gradient launch
            covers 64 hidden columns per workgroup in fp32, 128 in bf16 below hidden_dim 128, 160 in bf16 at hidden_dim 128;
            the small-gradient slots and the single-owner embedding gradients exist in bf16 only)
@@ -67,12 +67,12 @@ def _mm(name, image, text, fusion, B=5, p=0.0, K=5, **expect):
     return Case(name, "mmimdb", cfg, B, p, expect)
 
 
-def _mimic(name, num_patch, B=13, D=64, **expect):
-    cfg = dict(dropout=0.0, num_classes=6,
-               time=dict(embedding_dim=12, proj_dim=D, hidden_dim=D, num_patch=num_patch, token_dim=16, channel_dim=33, num_mixers=1),
+def _mimic(name, num_patch, B=13, D=64, p=0.0, time_mixers=1, **expect):
+    cfg = dict(dropout=p, num_classes=6,
+               time=dict(embedding_dim=12, proj_dim=D, hidden_dim=D, num_patch=num_patch, token_dim=16, channel_dim=33, num_mixers=time_mixers),
                static=dict(input_dim=5, hidden_dim=24, num_blocks=2, output_dim=D),
                multimodal=dict(hidden_dim=D, token_dim=8, channel_dim=100, num_mixers=1))
-    return Case(name, "mimic", cfg, B, 0.0, expect)
+    return Case(name, "mimic", cfg, B, p, expect)
 
 
 # token counts from small images: (4, 4) / 4 -> 1, (8, 4) / 4 -> 2, (12, 4) / 4 -> 3, (8, 8) / 4 -> 4, (8, 12) / 4 -> 6,
@@ -157,4 +157,13 @@ CASES = [
     _mimic("mimic_patches_8", 8, time_wide=False, wide_fus=True, heads_pool=True, mlp_ride=True),
     # past batch 2048 the MLP has launches of its own and the step runs on three streams with per-segment Adam
     _mimic("mimic_patches_9_b2049", 9, B=2049, D=32, time_wide=True, wide_fus=True, mlp_ride=False),
+    # dropout on: the static MLP's masks are the host replica's.  The flushed ride under the one-bit and the 16-bit stream ...
+    _mimic("mimic_patches_7_half", 7, p=0.5, time_wide=False, wide_fus=False, heads_pool=True, mlp_ride=True),
+    _mimic("mimic_patches_8_gen", 8, p=0.1, time_wide=False, wide_fus=True, heads_pool=True, mlp_ride=True),
+    # ... and the MLP riding in a wide time tower's token-mixing launch (the carrier draws masks of its own in the same launch).
+    # Two time blocks: with one, hidden_dim 32 at batch 13 has too few parameters for the stale-parameter condition of
+    # tests/test_host_engine_cases.py (step-2 logits move by 0.125 < 10 x the bf16 bar; 0.232 with two)
+    _mimic("mimic_patches_9_wide_carrier_half", 9, D=32, p=0.5, time_mixers=2, time_wide=True, wide_fus=True, heads_pool=True, mlp_ride=True),
+    # past batch 2048 with dropout: the MLP's own launches (VALU kernels) beside the towers on three streams
+    _mimic("mimic_patches_9_b2049_gen", 9, B=2049, D=32, p=0.3, time_wide=True, wide_fus=True, mlp_ride=False),
 ]

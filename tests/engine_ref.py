@@ -5,6 +5,7 @@ from collections import OrderedDict
 
 import torch
 
+import drop_ref as DR
 import gen_util as G
 from oracle import m2mixer_oracle as O
 
@@ -12,8 +13,8 @@ NOISE_KEYS = ("token_mix.2.net.3.bias",)       # rounding-level gradient under a
 
 
 def p_effective(p):
-    """The keep probability is quantised to 16 bits; the kernels scale by 1 / keep_q."""
-    return 1 - round((1 - p) * 65536) / 65536
+    """The keep probability is quantised to 16 bits; the kernels scale by 1 / keep_q (drop_ref.drop_thr: the library's rounding)."""
+    return DR.p_effective(p)
 
 
 def grads_cleared(eng):
@@ -55,10 +56,32 @@ def tower_masks(rt, B, seed, step):
     return blocks
 
 
+def mlp_masks(mlp, B, seed, step):
+    """The keep-masks of the plain MLP's hidden layers at `step`, from the host replica of the dropout stream (tests/drop_ref.py:
+    the MLP has no mask probe): one (B, width) tensor per hidden layer, as oracle.mlp takes them."""
+    d = mlp.desc
+    return [torch.from_numpy(DR.mlp_mask(seed, step, d.site_base, l, d.p_drop, B, mlp.dims[l + 1])).float()
+            for l in range(mlp.nlayers - int(mlp.has_out))]
+
+
 def engine_masks(eng, B):
-    """The keep-masks of every dropout site of a two-tower engine's three towers at its current step."""
+    """The keep-masks of every dropout site of an engine at its current step: the three towers of a two-tower engine, or the MIMIC
+    engine's two towers ("time", "fusion") and its static MLP ("static")."""
+    from m2_mixer_amd.engine import MimicEngine
     step, seed = int(eng.drop_step[0]), eng.seed
+    if isinstance(eng, MimicEngine):
+        return {"time": tower_masks(eng.t_time, B, seed, step), "fusion": tower_masks(eng.t_fus, B, seed, step),
+                "static": mlp_masks(eng.mlp, B, seed, step)}
     return {name: tower_masks(rt, B, seed, step) for name, rt in ((eng.MODS[0], eng.t_a), (eng.MODS[1], eng.t_b), ("fusion", eng.t_fus))}
+
+
+def masks_equal(a, b):
+    """Two results of engine_masks (or None: dropout off) hold the same masks.  A group is a list: one dict of site masks per tower
+    block, or one tensor per hidden layer of the MIMIC engine's static MLP."""
+    if a is None or b is None:
+        return a is b
+    flat = lambda m: [t for n in m for x in m[n] for t in (x.values() if isinstance(x, dict) else (x,))]
+    return len(flat(a)) == len(flat(b)) and all(torch.equal(x, y) for x, y in zip(flat(a), flat(b)))
 
 
 # ---- the case table's engines ------------------------------------------------------------------------------------------------

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 import torch
 
+import drop_ref as DR
 import gen_util as G
 from conftest import observe
 from golden_util import check, load
@@ -145,7 +146,7 @@ def test_block_dropout_masks_match_oracle(case, p_drop, dev):
     masks = {"tok_h": rt.dropout_mask(0, 0, B, sd, st).view(B, D, T), "tok_o": rt.dropout_mask(0, 1, B, sd, st).view(B, D, N),
              "ch_h": rt.dropout_mask(0, 2, B, sd, st).view(B, N, rt.Cp)[:, :, :Cc], "ch_o": rt.dropout_mask(0, 3, B, sd, st).view(B, N, D)}
     masks = {k: v.float().cpu() for k, v in masks.items()}
-    thr = round((1 - p_drop) * 65536)
+    thr = DR.drop_thr(p_drop)
     p_eff = 1 - thr / 65536            # keep probability is quantised to 16 bits; the kernels scale by 1/(1-p_eff)
     for k, m in masks.items():
         tol = max(0.03, 5 * 0.5 / m.numel() ** 0.5)      # 5 sigma of a Bernoulli mean over the mask's elements
@@ -761,7 +762,7 @@ def test_static_mlp_dropout_consistency(dev):
     rt.forward(x, B, out, 3 * cs["output_dim"], dense, True, 123, 1)
     torch.cuda.synchronize()
     acts = [a.cpu() for a in rt._keep["act"][:2]]
-    thr = round((1 - p_drop) * 65536)
+    thr = DR.drop_thr(p_drop)
     scale = 65536.0 / thr
     leaves = {k[len("static_extractor."):]: v.detach().cpu().clone().requires_grad_(True) for k, v in params.items()}
     h = x.cpu()

@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+import drop_ref as DR
 import leaf_ref as R
 from conftest import observe
 from oracle import m2mixer_oracle as O
@@ -344,7 +345,7 @@ def test_mlp_large_batch_vs_float64(dims, has_out, p_drop, B, dev):
     rt, params, dp, grads, x = mlp_setup(dims, has_out, p_drop, B, dev)
     xg, dout, nhid = x.to(dev), dims[-1], len(dims) - 1 - int(has_out)
     out, dense, acts = mlp_forward(rt, xg, B, dout, True, 1, dev)
-    thr = round((1 - p_drop) * 65536)
+    thr = DR.drop_thr(p_drop)
     keep_q = thr / 65536
     leaves = {k: v.double().requires_grad_(True) for k, v in params.items()}
     h, masks = x.double(), []

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+import drop_ref as DR
 import gen_util as G
 from conftest import observe
 from oracle import m2mixer_oracle as O
@@ -192,7 +193,7 @@ def test_shape_envelope_vs_float64_oracle(case, prec, dev, precision):
     mod, params, x, dy, y, xd = run_case(case, prec, dev)
     drop_p, masks = 0.0, None
     if case.p > 0:
-        thr = round((1 - case.p) * 65536)
+        thr = DR.drop_thr(case.p)
         drop_p = 1 - thr / 65536                 # the kernels' 16-bit keep probability
         masks = kernel_masks(mod, case)
     leaves = {k: v.double().requires_grad_(True) for k, v in params.items()}

@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 import torch
 
+import drop_ref as DR
 import gen_util as G
 import split_cases as SC
 from conftest import observe
@@ -28,7 +29,7 @@ NAN0 = 0x7FC00000        # quiet NaN; the low bits carry the element index, so a
 
 
 def p_effective(p):
-    return 1 - round((1 - p) * 65536) / 65536 if p > 0 else 0.0          # the kernels' 16-bit keep probability
+    return DR.p_effective(p) if p > 0 else 0.0          # the kernels' 16-bit keep probability
 
 
 def nan_fill(t):

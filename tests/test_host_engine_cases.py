@@ -19,13 +19,17 @@ def test_table_hygiene():
         assert c.engine in ("avmnist", "mmimdb", "mimic"), c.name
         assert c.expect and set(c.expect) <= set(DECISIONS), (c.name, set(c.expect) - set(DECISIONS))
         assert c.cfg["dropout"] == c.p and 0.0 <= c.p < 1.0, c.name
-        assert c.engine != "mimic" or c.p == 0.0, "the MIMIC cases stay at p = 0 (no mask export for the static MLP)"
         for v in c.expect.values():
             assert not isinstance(v, dict) or set(v) == {"fp32", "bf16"}, c.name
     # dropout is spread over the cases: off, the one-bit stream and a general rate; masks in a grouped and an ungrouped case
     assert {0.0, 0.5} <= {c.p for c in CASES} and any(c.p not in (0.0, 0.5) for c in CASES)
     for grouped in (True, False):
         assert any(c.p > 0 and c.expect.get("grouped") is grouped for c in CASES), grouped
+    # MIMIC with dropout: both streams, the riding MLP flushed on its own (fused time tower) and carried (wide time tower)
+    mimic = [c for c in CASES if c.engine == "mimic" and c.p > 0]
+    assert 0.5 in {c.p for c in mimic} and any(c.p != 0.5 for c in mimic)
+    for time_wide in (True, False):
+        assert any(c.expect.get("mlp_ride") is True and c.expect.get("time_wide") is time_wide for c in mimic), time_wide
 
 
 def _values(decision):
@@ -72,3 +76,43 @@ def test_reference_runs_and_a_stale_parameter_set_would_show(case):
     stale2 = ref.forward(b2, {k: v.double() for k, v in params.items()})["logits"]
     gap = float((true2 - stale2).abs().max())
     assert gap >= 10 * BF16_LOGITS, f"{case.name}: stale parameters move the step-2 logits by {gap:.3f} only"
+
+
+def random_masks(case, seed):
+    """Random keep-masks (rate 1 - p) for the three mask groups of a MIMIC case, in the layouts oracle.mimic_forward takes."""
+    gen = torch.Generator().manual_seed(seed)
+    keep = 1 - R.p_effective(case.p or 0.5)
+    draw = lambda *shape: (torch.rand(*shape, generator=gen) < keep).double()
+    B, ct, cs, cm = case.B, case.cfg["time"], case.cfg["static"], case.cfg["multimodal"]
+
+    def tower(c, N):
+        D, T, C = c["hidden_dim"], c["token_dim"], c["channel_dim"]
+        return [{"tok_h": draw(B, D, T), "tok_o": draw(B, D, N), "ch_h": draw(B, N, C), "ch_o": draw(B, N, D)} for _ in range(c["num_mixers"])]
+
+    return {"time": tower(ct, ct["num_patch"]), "fusion": tower(cm, 1 + ct["num_patch"]),
+            "static": [draw(B, cs["hidden_dim"]) for _ in range(cs["num_blocks"])]}
+
+
+MIMIC_CASES = [c for c in CASES if c.engine == "mimic"]
+
+
+@pytest.mark.parametrize("case", MIMIC_CASES, ids=[c.name for c in MIMIC_CASES])
+def test_mimic_reference_takes_masks_in_all_three_groups(case):
+    """The float64 MIMIC reference under random keep-masks for the time tower, the fusion tower and the static MLP (the successor of
+    "the MIMIC cases stay at p = 0"): finite, and every group's masks reach the loss -- replacing one group's masks by all-ones
+    moves it.  On the cases with dropout the reference's whole step (autograd + Adam) runs with the masks."""
+    params = {k: v.double() for k, v in G.make_params(R.case_shapes(case), PARAM_SEED).items()}
+    batch, masks = R.case_batch(case, 101), random_masks(case, 7)
+    drop_p = R.p_effective(case.p or 0.5)
+    ones = lambda m: {k: torch.ones_like(v) for k, v in m.items()} if isinstance(m, dict) else torch.ones_like(m)
+    with torch.no_grad():
+        full = R.case_forward(case, batch, params, drop_p, masks)
+        assert bool(torch.isfinite(full["logits"]).all()) and bool(torch.isfinite(full["losses"]).all())
+        for group in ("time", "fusion", "static"):
+            other = dict(masks, **{group: [ones(m) for m in masks[group]]})
+            moved = float((R.case_forward(case, batch, params, drop_p, other)["losses"] - full["losses"]).abs().max())
+            assert moved > 1e-3, (group, moved)
+    if case.p > 0:
+        out = R.Step(case, params, LR).step(batch, masks)
+        assert torch.equal(out["losses"], full["losses"])
+        assert all(bool(torch.isfinite(g).all()) and float(g.abs().max()) > 0 for k, g in out["grads"].items() if not k.endswith(R.NOISE_KEYS))
