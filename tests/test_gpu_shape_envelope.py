@@ -164,11 +164,14 @@ def oracle(case, x, p, drop_p, masks):
     return O.mlp_mixer_no_patching(x, p, "", case.nb, drop_p, masks)
 
 
-def run_case(case, prec, dev, seed=0):
-    """(module, params, x, dy, y, x_dev) after one training-mode forward + backward on the GPU."""
+def run_case(case, prec, dev, seed=0, transform=None):
+    """(module, params, x, dy, y, x_dev) after one training-mode forward + backward on the GPU.  transform: (params, x) ->
+    (params, x) applied to the generated tensors first (tests/value_cases.py)."""
     params = G.make_params(case_shapes(case), 4242 + seed)
     rng = np.random.default_rng(977 + seed)
     x = make_input(case, rng)
+    if transform is not None:
+        params, x = transform(params, x)
     mod = make_module(case).to(dev)
     mod.load_state_dict(params)
     mod.train()
