@@ -2,7 +2,7 @@
 // uncertainty-based late fusion of the heads' predictions in a second, small one behind it.
 //
 // Reference: models/avmnist.py:447-572 (AVMnistMixerMultiLossUQ) with modules/losses.py:5-31 (EDLMSELoss).  Per head and sample,
-// z = the head's K logits (the same Linear on the token mean as heads.hip), y = the one-hot label:
+// z = the head's K logits (a Linear on the token mean: heads_body.h), y = the one-hot label:
 //     e = relu(z), a = e + 1, S = sum_k a_k, p = a / S
 //     L = sum_k [(y_k - p_k)^2 + p_k (1 - p_k) / (S + 1)]        loss_h = mean over the batch        (losses.py:24-31)
 //     total = sum_h coef_h loss_h                                  (avmnist.py:511: coefficients 1, 1, 1, no x 3)
@@ -16,9 +16,9 @@
 //     dE_j = (-2 / S) [(y_j - p_j) - sum_k (y_k - p_k) p_k]
 //     dV_j = (-2 / (S (S + 1))) (p_j - sum_k p_k^2) - (1 - sum_k p_k^2) / (S + 1)^2
 // with every 1 / (S (S + 1)) and 1 / (S + 1)^2 taken as two divisions (a very large S must not overflow a product).
-// Everything is fp32.  The phases around the loss -- pooled rows and weights into LDS, logits, d_pooled, g_w / g_b or the g_part
-// slots -- are those of heads.hip's cross-entropy kernel on the same grid (m2m_heads_part_tiles(B) sample tiles x heads), so the
-// unchanged m2m_towers_wgrad_heads adds the slots.
+// Everything is fp32.  This file holds the loss phase; the phases around it -- pooled rows and weights into LDS, logits, the block's
+// loss sum, d_pooled, g_w / g_b or the g_part slots that m2m_towers_wgrad_heads adds -- the grid and the argument checks are
+// heads_body.h's and heads.hip's host side (host.h).
 //
 // m2m_heads_edl_risk adds the two pieces of modules/losses.py the reference's UQ model does not train with -- the cross-entropy
 // Bayes risk (EDLCELoss, modules/losses.py:71-93) and the Dirichlet KL regulariser (modules/losses.py:33-49 and :52-68, the same
@@ -32,15 +32,10 @@
 // the presence of the KL term are template parameters: <MSE, no KL> is the kernel m2m_heads_edl always launched.  lambda is one
 // device float (a captured graph follows it); lambda == 0 takes a workgroup-uniform branch round all KL arithmetic, so that form
 // costs nothing, equals the no-KL result bit for bit, and an overflowing lgamma never meets a zero factor.
-#include "dispatch.h"
-
-#define EDL_S 16        // samples per workgroup (4 at B <= 64): the grid of heads.hip
-#define EDL_MAXK 32
-#define EDL_MAXH 4
+#include "heads_body.h"
 
 struct EdlArgs {
-    m2m_head h[EDL_MAXH];
-    const float* weights;       // nheads device floats read in place of m2m_head.weight, or NULL
+    HeadArgs heads;
     const float* kl_coef;       // (KL instantiations) one device float: lambda
     float* kl_out;              // (KL instantiations) nheads floats += the unscaled batch-mean KL, or NULL
     float lgamma_k;             // lgamma(K), from the host
@@ -97,92 +92,18 @@ __global__ __launch_bounds__(NTHREADS) void heads_edl_kernel(const EdlArgs ha, c
                                                              float* __restrict__ logits_out, float* __restrict__ losses,
                                                              int32_t* __restrict__ preds, float* __restrict__ uncertainty,
                                                              int nheads) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int D = DD, DL = DD + 4, D4 = DD / 4;
-    float* pl = reinterpret_cast<float*>(smem);          // pooled tile [S][DL]
-    float* wl = pl + S * DL;                              // weights     [EDL_MAXK][DL]
-    float* lg = wl + EDL_MAXK * DL;                       // logits / dlogits [S][EDL_MAXK]
-    float* red = lg + S * EDL_MAXK;                       // [S] loss terms
-    float* klr = red + S;                                 // [S] KL terms (KL instantiations only: the others have no such array)
+    HEADS_TILE(ha.heads)
+    float* klr = ext;                                     // [S] KL terms (KL instantiations only: the others have no such array)
 
-    const int tid = threadIdx.x;
-    const int hI = blockIdx.y;
-    const m2m_head& hd = ha.h[hI];
-    const float hw = ha.weights ? ha.weights[hI] : hd.weight;      // this head's coefficient in the total loss
-    const int s0 = blockIdx.x * S;
-    const int ns = min(S, B - s0);
-
-    // ---- pooled rows and head weights -> LDS (16-byte accesses; every global load requested before the first LDS write) ----
-    {
-        constexpr int NP = (S * D4 + NTHREADS - 1) / NTHREADS, NW = (EDL_MAXK * D4 + NTHREADS - 1) / NTHREADS;
-        f32x4_t pv[NP], wv[NW];
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int idx = tid + i * NTHREADS, sI = idx / D4, c = (idx % D4) * 4;
-            pv[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            if (idx < S * D4 && sI < ns) {
-                if (hd.tokens) {
-                    // x.mean(dim=1): tokens in order, eight loads in flight, the 1 / N product (the bits of heads.hip's pooling)
-                    const float* col = hd.tokens + (long)(s0 + sI) * hd.tok_sample_stride + c;
-                    const int N = hd.ntok;
-                    f32x4_t a = f32x4_t{0.f, 0.f, 0.f, 0.f};
-                    for (int n0 = 0; n0 < N; n0 += 8) {
-                        f32x4_t t8[8];
-#pragma unroll
-                        for (int j = 0; j < 8; ++j) t8[j] = *reinterpret_cast<const f32x4_t*>(col + (long)min(n0 + j, N - 1) * D);
-#pragma unroll
-                        for (int j = 0; j < 8; ++j)
-                            if (n0 + j < N) a += t8[j];
-                    }
-                    pv[i] = a * (1.0f / (float)N);
-                } else pv[i] = *reinterpret_cast<const f32x4_t*>(hd.pooled + (long)(s0 + sI) * D + c);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-            const int idx = tid + i * NTHREADS;
-            wv[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            if (idx < K * D4) wv[i] = *reinterpret_cast<const f32x4_t*>(hd.w + (long)idx * 4);
-        }
-#pragma unroll
-        for (int i = 0; i < NP; ++i) {
-            const int idx = tid + i * NTHREADS;
-            if (idx < S * D4) *reinterpret_cast<f32x4_t*>(pl + (idx / D4) * DL + (idx % D4) * 4) = pv[i];      // rows >= ns: zeros
-        }
-#pragma unroll
-        for (int i = 0; i < NW; ++i) {
-            const int idx = tid + i * NTHREADS;
-            if (idx < EDL_MAXK * D4) *reinterpret_cast<f32x4_t*>(wl + (idx / D4) * DL + (idx % D4) * 4) = wv[i];     // rows >= K: zeros
-        }
-    }
+    HEADS_STAGE()
     __syncthreads();
-    // ---- logits: 4 adjacent lanes split each D-long dot product, float4 chunks interleaved over the lanes ----
-    for (int idx = tid >> 2; idx < S * K; idx += NTHREADS / 4) {
-        const int sI = idx / K, k = idx % K, part = tid & 3;
-        constexpr int NC = D4 / 4;                        // float4 chunks per lane
-        f32x4_t a4[NC], b4[NC];
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            a4[c] = *reinterpret_cast<const f32x4_t*>(pl + sI * DL + 4 * (part + 4 * c));
-            b4[c] = *reinterpret_cast<const f32x4_t*>(wl + k * DL + 4 * (part + 4 * c));
-        }
-        float a = 0.f;
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) a = __builtin_fmaf(a4[c][e], b4[c][e], a);
-        a = wave_sum_xor(a, 4) + hd.b[k];
-        if (part == 0) {
-            lg[sI * EDL_MAXK + k] = a;
-            if (sI < ns) logits_out[((long)hI * B + s0 + sI) * K + k] = a;
-        }
-    }
+    HEADS_LOGITS()
     __syncthreads();
-    // ---- loss / prediction / uncertainty / dlogits: 32 lanes per sample, lane k holds logit k (K <= EDL_MAXK = 32) ----
+    // ---- loss / prediction / uncertainty / dlogits: 32 lanes per sample, lane k holds logit k (K <= HEAD_MAXK = 32) ----
     if (tid < S * 32) {
         const int sI = tid >> 5, k = tid & 31;
         const bool live = k < K;
-        const float z = live ? lg[sI * EDL_MAXK + k] : 0.f;
+        const float z = live ? lg[sI * HEAD_MAXK + k] : 0.f;
         const float ev = __builtin_fmaxf(z, 0.f);             // evidence
         const float al = live ? ev + 1.f : 0.f;               // alpha (dead lanes add nothing to the sums)
         float mx = live ? ev : -1.f;                          // argmax of the evidence, first index of the maximum
@@ -240,7 +161,7 @@ __global__ __launch_bounds__(NTHREADS) void heads_edl_kernel(const EdlArgs ha, c
                 if (k == 0) klr[sI] = sI < ns ? kl : 0.f;
             }
         }
-        if (live) lg[sI * EDL_MAXK + k] = dl;
+        if (live) lg[sI * HEAD_MAXK + k] = dl;
         if (k == 0) {
             red[sI] = sI < ns ? term : 0.f;
             if (sI < ns) {
@@ -250,66 +171,11 @@ __global__ __launch_bounds__(NTHREADS) void heads_edl_kernel(const EdlArgs ha, c
         }
     }
     __syncthreads();
-    if (tid == 0) {
-        float t = 0.f;
-#pragma unroll
-        for (int sI = 0; sI < S; ++sI) t += red[sI];
-        t /= (float)B;
-        if constexpr (KL) {
-            const float lam = *ha.kl_coef;
-            if (lam != 0.f) {                                 // (the loss phase's branch: klr was written)
-                float tk = 0.f;
-#pragma unroll
-                for (int sI = 0; sI < S; ++sI) tk += klr[sI];
-                tk /= (float)B;
-                t += lam * tk;
-                if (ha.kl_out) atomicAdd(ha.kl_out + hI, tk);
-            }
-        }
-        atomicAdd(losses + hI, t);
-        atomicAdd(losses + nheads, t * hw);
-    }
-    if (hd.d_pooled) {
-        // d_pooled[s][d..d+3] = sum_k dl[s][k] w[k][d..d+3]: thread = (sample, float4 of d)
-        for (int idx = tid; idx < ns * D4; idx += NTHREADS) {
-            const int sI = idx / D4, c = (idx % D4) * 4;
-            f32x4_t a = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            for (int k = 0; k < K; ++k) {
-                const f32x4_t w4 = *reinterpret_cast<const f32x4_t*>(wl + k * DL + c);
-                const float dk = lg[sI * EDL_MAXK + k];
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a[e] = __builtin_fmaf(dk, w4[e], a[e]);
-            }
-            *reinterpret_cast<f32x4_t*>(hd.d_pooled + (long)(s0 + sI) * D + c) = a;
-        }
-        // g_part: this workgroup's sums go to its slot (plain stores; m2m_towers_wgrad_heads adds the slots in a fixed order)
-        // g_w[k][d..d+3] = sum_s dl[s][k] pooled[s][d..d+3]: thread = (class, float4 of d), the sample loop unrolled
-        float* slot = hd.g_part ? hd.g_part + (long)blockIdx.x * M2M_SPLIT_GPART : nullptr;
-        for (int idx = tid; idx < K * D4; idx += NTHREADS) {
-            const int k = idx / D4, c = (idx % D4) * 4;
-            f32x4_t a = f32x4_t{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int sI = 0; sI < S; ++sI) {
-                const f32x4_t p4 = *reinterpret_cast<const f32x4_t*>(pl + sI * DL + c);
-                const float d1 = lg[sI * EDL_MAXK + k];       // samples >= ns: 0
-#pragma unroll
-                for (int e = 0; e < 4; ++e) a[e] = __builtin_fmaf(d1, p4[e], a[e]);
-            }
-            if (slot) *reinterpret_cast<f32x4_t*>(slot + (long)k * D + c) = a;
-            else {
-#pragma unroll
-                for (int e = 0; e < 4; ++e) atomicAdd(hd.g_w + (long)k * D + c + e, a[e]);
-            }
-        }
-        if (tid < K) {
-            float a = 0.f;
-#pragma unroll
-            for (int sI = 0; sI < S; ++sI) a += lg[sI * EDL_MAXK + tid];
-            if (slot) slot[K * D + tid] = a;
-            else atomicAdd(hd.g_b + tid, a);
-        }
-        if (slot && tid < 2) slot[K * D + K + tid] = 0.f;           // (the slot layout's loss entries: the losses stay atomics)
-    }
+    if constexpr (KL) {
+        const float lam = *ha.kl_coef;                        // (the loss phase's branch: klr was written where lam != 0)
+        heads_loss_sum<S>(red, tid, hI, hw, B, losses, nheads, lam != 0.f ? klr : nullptr, lam, ha.kl_out);
+    } else heads_loss_sum<S>(red, tid, hI, hw, B, losses, nheads);
+    HEADS_BACKWARD()
 }
 
 // The late fusion of avmnist.py:533-537, one thread per sample: the prediction of the head whose uncertainty is strictly below
@@ -330,28 +196,20 @@ __global__ void edl_combine_kernel(const int32_t* preds, const float* __restrict
     combined[i] = strict ? pick : 0;
 }
 
-// (the losses are cleared by a kernel, as in heads.hip: a small memset node misbehaved on hipGraph replay)
-__global__ void edl_zero_floats_kernel(float* p, int n, float* q, int nq) {
-    if ((int)threadIdx.x < n) p[threadIdx.x] = 0.f;
-    if ((int)threadIdx.x < nq) q[threadIdx.x] = 0.f;         // (kl_out, cleared together with the losses)
-}
-
 template <int S, int RISK, bool KL>
 static int launch_edl_s(const EdlArgs& ha, int nheads, const int64_t* labels, int B, int D, int K, float* logits, float* losses,
                         int32_t* preds, float* uncertainty, hipStream_t st) {
     return m2m_dispatch(m2m_wide_dims{}, D, M2M_NO_BUILD, [&](auto DD) {
-        constexpr int Dc = decltype(DD)::value;
-        const size_t lds = sizeof(float) * ((size_t)S * (Dc + 4) + (size_t)EDL_MAXK * (Dc + 4) + S * EDL_MAXK + S + (KL ? S : 0));
-        return m2m_launch<heads_edl_kernel<S, Dc, RISK, KL>>(dim3((B + S - 1) / S, nheads), dim3(NTHREADS), lds, 160 * 1024, st, ha, labels,
-                                                             B, K, logits, losses, preds, uncertainty, nheads);
+        return m2m_launch<heads_edl_kernel<S, DD(), RISK, KL>>(dim3((B + S - 1) / S, nheads), dim3(NTHREADS), heads_lds_bytes(S, DD(), KL ? S : 0),
+                                                               160 * 1024, st, ha, labels, B, K, logits, losses, preds, uncertainty, nheads);
     });
 }
 
 template <int RISK, bool KL>
-static int launch_edl(int S, const EdlArgs& ha, int nheads, const int64_t* labels, int B, int D, int K, float* logits, float* losses,
+static int launch_edl(const EdlArgs& ha, int nheads, const int64_t* labels, int B, int D, int K, float* logits, float* losses,
                       int32_t* preds, float* uncertainty, hipStream_t st) {
-    return S == 4 ? launch_edl_s<4, RISK, KL>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st)
-                  : launch_edl_s<EDL_S, RISK, KL>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st);
+    return heads_samples_per_wg(B) == 4 ? launch_edl_s<4, RISK, KL>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st)
+                                        : launch_edl_s<HEAD_S, RISK, KL>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st);
 }
 
 extern "C" int m2m_heads_edl_risk(const m2m_head* heads, int nheads, const int64_t* labels, int B, int D, int K, float* logits,
@@ -365,55 +223,21 @@ extern "C" int m2m_heads_edl_risk(const m2m_head* heads, int nheads, const int64
         m2m_set_error("heads_edl: kl_out needs kl_coef (without the KL term there is nothing to report)", __FILE__, __LINE__);
         return -1;
     }
-    if (!heads || nheads < 1 || nheads > EDL_MAXH || K < 2 || K > EDL_MAXK || B < 1) {
-        m2m_set_error("heads_edl: unsupported (1..4 heads, K in 2..32, B >= 1)", __FILE__, __LINE__);
+    if (int rc = m2m_check_heads("heads_edl", heads, nheads, labels, B, D, K, logits, losses, preds, false, M2M_SPLIT_GPART)) return rc;
+    if (!uncertainty || !combined) {
+        m2m_set_error("heads_edl: uncertainty and combined are required", __FILE__, __LINE__);
         return -1;
     }
-    if (D != 32 && D != 64 && D != 128 && D != 256) {      // before anything is launched (the losses' zero fill below)
-        m2m_set_error("heads_edl: hidden_dim must be 32, 64, 128 or 256", __FILE__, __LINE__);
-        return -1;
-    }
-    if (!labels || !logits || !losses || !preds || !uncertainty || !combined) {
-        m2m_set_error("heads_edl: labels, logits, losses, preds, uncertainty and combined are required", __FILE__, __LINE__);
-        return -1;
-    }
-    const int S = B <= 64 ? 4 : EDL_S;
-    if ((B + S - 1) / S != m2m_heads_part_tiles(B)) {      // the slot count m2m_towers_wgrad_heads adds
-        m2m_set_error("heads_edl: its sample tiles are not those of m2m_heads_part_tiles", __FILE__, __LINE__);
-        return -1;
-    }
-    EdlArgs ha;
-    for (int i = 0; i < nheads; ++i) {
-        if (heads[i].tokens ? (heads[i].ntok < 1 || heads[i].tok_sample_stride < (int64_t)heads[i].ntok * D || (heads[i].tok_sample_stride & 3) ||
-                               (reinterpret_cast<uintptr_t>(heads[i].tokens) & 15))
-                            : !heads[i].pooled) {
-            m2m_set_error("heads_edl: a head needs pooled, or 16-byte aligned tokens with ntok >= 1 and a sample stride >= ntok * D (multiple of 4)", __FILE__, __LINE__);
-            return -1;
-        }
-        if (!heads[i].w || !heads[i].b || (heads[i].d_pooled && !heads[i].g_part && (!heads[i].g_w || !heads[i].g_b))) {
-            m2m_set_error("heads_edl: a head needs w and b, and with d_pooled either g_part or g_w and g_b", __FILE__, __LINE__);
-            return -1;
-        }
-        if (heads[i].g_part && (long)K * D + K + 2 > M2M_SPLIT_GPART) {
-            m2m_set_error("heads_edl: g_part needs K*D + K + 2 <= M2M_SPLIT_GPART", __FILE__, __LINE__);
-            return -1;
-        }
-    }
-    ha.weights = weights;
-    ha.kl_coef = kl_coef;
-    ha.kl_out = kl_out;
-    ha.lgamma_k = (float)lgamma((double)K);
-    for (int i = 0; i < nheads; ++i) ha.h[i] = heads[i];
-    for (int i = nheads; i < EDL_MAXH; ++i) ha.h[i] = heads[0];
+    const EdlArgs ha{heads_args(heads, nheads, weights), kl_coef, kl_out, (float)lgamma((double)K)};
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    if (zero_losses) hipLaunchKernelGGL(edl_zero_floats_kernel, dim3(1), dim3(64), 0, st, losses, nheads + 1, kl_out, kl_out ? nheads : 0);
+    if (zero_losses) m2m_heads_zero(losses, nheads + 1, kl_out, nheads, st);
     int rc;
     if (risk == M2M_EDL_MSE) {
-        rc = kl_coef ? launch_edl<M2M_EDL_MSE, true>(S, ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st)
-                     : launch_edl<M2M_EDL_MSE, false>(S, ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st);
+        rc = kl_coef ? launch_edl<M2M_EDL_MSE, true>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st)
+                     : launch_edl<M2M_EDL_MSE, false>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st);
     } else {
-        rc = kl_coef ? launch_edl<M2M_EDL_CE, true>(S, ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st)
-                     : launch_edl<M2M_EDL_CE, false>(S, ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st);
+        rc = kl_coef ? launch_edl<M2M_EDL_CE, true>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st)
+                     : launch_edl<M2M_EDL_CE, false>(ha, nheads, labels, B, D, K, logits, losses, preds, uncertainty, st);
     }
     if (rc != 0) return rc;
     hipLaunchKernelGGL(edl_combine_kernel, dim3((B + 255) / 256), dim3(256), 0, st, preds, uncertainty, combined, B, nheads);

@@ -24,6 +24,17 @@ static inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 // ---- embed.hip -----------------------------------------------------------------------------------------------------------------
 int m2m_check_embed(const m2m_embed* e, int B);
 
+// ---- heads.hip: the host side that the cross-entropy, BCE and evidential (edl.hip) heads share ---------------------------------
+// Samples per workgroup of every heads launch at batch B: its grid, and the slot count of m2m_heads_part_tiles.
+int heads_samples_per_wg(int B);
+// 0, or -1 with the error set ("<call>: ..."), before anything is launched: 1..4 heads, K in 2..32, B >= 1, a hidden_dim that is
+// built; labels (BCE: targets), logits, losses and preds given; per head pooled or well-formed tokens, w and b, and with d_pooled
+// either g_part or both of g_w and g_b.  g_part is refused for `bce` heads and where K*D + K + 2 exceeds slot_floats.
+int m2m_check_heads(const char* call, const m2m_head* heads, int nheads, const void* labels, int B, int D, int K, const float* logits,
+                    const float* losses, const int32_t* preds, bool bce, long slot_floats);
+// One launch that clears losses[0..n) and, where kl_out is given, kl_out[0..nkl).
+void m2m_heads_zero(float* losses, int n, float* kl_out, int nkl, hipStream_t st);
+
 // ---- tower_fwd.hip -------------------------------------------------------------------------------------------------------------
 // True when two towers can share one chain launch: both on the fused path, same kernel instantiation, <= 4 blocks each.
 bool m2m_can_group(const m2m_tower* a, const m2m_tower* b);

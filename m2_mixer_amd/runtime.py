@@ -755,10 +755,24 @@ def _head_array(heads: Sequence[dict]):
     return arr
 
 
-def _check_weights(weights: Optional[torch.Tensor], nh: int):
-    if weights is not None and (not weights.is_cuda or weights.dtype != torch.float32 or weights.numel() < nh
-                                or not weights.is_contiguous()):
-        raise ValueError(f"head weights: a contiguous float32 device tensor of at least {nh} entries")
+def _heads_call(kind: str, heads: Sequence[dict], like: torch.Tensor, B: int, K: int, out, weights: Optional[torch.Tensor],
+                kl: Sequence[tuple] = ()):
+    """What heads_ce / heads_bce / heads_edl share: the device tensors of the optional arguments checked (weights: nh floats;
+    kl: (name, tensor or None, entries)), the m2m_head array, and -- unless `out` is given -- the outputs on `like`'s device:
+    logits (nh, B, K), losses (nh + 1), preds (int32: (nh, B, K) for "bce", else (nh, B)) and, for "edl", uncertainty (nh, B)
+    and combined (B) int32.  Returns (nh, array, outputs)."""
+    nh = len(heads)
+    for name, t, n in (("head weights", weights, nh),) + tuple(kl):
+        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.numel() < n or not t.is_contiguous()):
+            raise ValueError(f"heads_{kind}: {name}: a contiguous float32 device tensor of at least {n} entries")
+    arr = _head_array(heads)
+    if out is None:
+        dev = like.device
+        out = (torch.empty(nh, B, K, device=dev), torch.empty(nh + 1, device=dev),
+               torch.empty((nh, B, K) if kind == "bce" else (nh, B), dtype=torch.int32, device=dev))
+        if kind == "edl":
+            out += (torch.empty(nh, B, device=dev), torch.empty(B, dtype=torch.int32, device=dev))
+    return nh, arr, tuple(out)
 
 
 def heads_bce(heads: Sequence[dict], targets: torch.Tensor, pos_weight: torch.Tensor, B: int, D: int, K: int, out=None,
@@ -767,25 +781,16 @@ def heads_bce(heads: Sequence[dict], targets: torch.Tensor, pos_weight: torch.Te
     Returns logits (nh, B, K), losses (nh + 1), preds (nh, B, K) int32.
     weights: the heads' loss coefficients as a device tensor (m2m_heads_bce_w: read on every launch, so a captured graph follows
     changes to it); None: each head's `weight` (m2m_heads_bce)."""
-    nh = len(heads)
-    _check_weights(weights, nh)
-    arr = _head_array(heads)
+    nh, arr, out = _heads_call("bce", heads, targets, B, K, out, weights)
     _check_tensor(targets, (B, K), "BCE targets")
-    dev = targets.device
-    if out is not None:
-        logits, losses, preds = out
-    else:
-        logits = torch.empty(nh, B, K, device=dev)
-        losses = torch.empty(nh + 1, device=dev)
-        preds = torch.empty(nh, B, K, dtype=torch.int32, device=dev)
+    logits, losses, preds = out
+    args = (arr, nh, targets.data_ptr(), pos_weight.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(), preds.data_ptr(),
+            int(zero_losses))
     if weights is not None:
-        L.check(L.lib().m2m_heads_bce_w(arr, nh, targets.data_ptr(), pos_weight.data_ptr(), B, D, K, logits.data_ptr(),
-                                        losses.data_ptr(), preds.data_ptr(), int(zero_losses), weights.data_ptr(), L.stream_ptr()),
-                "heads_bce_w")
+        L.check(L.lib().m2m_heads_bce_w(*args, weights.data_ptr(), L.stream_ptr()), "heads_bce_w")
     else:
-        L.check(L.lib().m2m_heads_bce(arr, nh, targets.data_ptr(), pos_weight.data_ptr(), B, D, K, logits.data_ptr(),
-                                      losses.data_ptr(), preds.data_ptr(), int(zero_losses), L.stream_ptr()), "heads_bce")
-    return logits, losses, preds
+        L.check(L.lib().m2m_heads_bce(*args, L.stream_ptr()), "heads_bce")
+    return out
 
 
 def heads_ce(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: int, out=None, zero_losses: bool = True,
@@ -793,23 +798,14 @@ def heads_ce(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: int
     """heads: dicts with pooled, w, b, g_w, g_b, d_pooled (tensors or None) and weight.
     Returns logits (nh, B, K), losses (nh + 1), preds (nh, B) int32 (written into `out` if given).
     weights: the heads' loss coefficients as a device tensor (m2m_heads_ce_w), None: each head's `weight`."""
-    nh = len(heads)
-    _check_weights(weights, nh)
-    arr = _head_array(heads)
-    dev = labels.device
-    if out is not None:
-        logits, losses, preds = out
-    else:
-        logits = torch.empty(nh, B, K, device=dev)
-        losses = torch.empty(nh + 1, device=dev)
-        preds = torch.empty(nh, B, dtype=torch.int32, device=dev)
+    nh, arr, out = _heads_call("ce", heads, labels, B, K, out, weights)
+    logits, losses, preds = out
+    args = (arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(), preds.data_ptr(), int(zero_losses))
     if weights is not None:
-        L.check(L.lib().m2m_heads_ce_w(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(),
-                                       preds.data_ptr(), int(zero_losses), weights.data_ptr(), L.stream_ptr()), "heads_ce_w")
+        L.check(L.lib().m2m_heads_ce_w(*args, weights.data_ptr(), L.stream_ptr()), "heads_ce_w")
     else:
-        L.check(L.lib().m2m_heads_ce(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(),
-                                     preds.data_ptr(), int(zero_losses), L.stream_ptr()), "heads_ce")
-    return logits, losses, preds
+        L.check(L.lib().m2m_heads_ce(*args, L.stream_ptr()), "heads_ce")
+    return out
 
 
 def heads_edl(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: int, out=None, zero_losses: bool = True,
@@ -822,30 +818,15 @@ def heads_edl(heads: Sequence[dict], labels: torch.Tensor, B: int, D: int, K: in
     weights: the heads' loss coefficients as a device tensor, None: each head's `weight`.
     risk ("mse" / "ce"), kl_coef (one device float, lambda) and kl_out (nh device floats: += the unscaled batch-mean KL) select
     m2m_heads_edl_risk (modules/losses.py:71-93, :52-68); with none of the three the call is m2m_heads_edl, as before."""
-    nh = len(heads)
-    _check_weights(weights, nh)
     if risk is not None and risk not in L.EDL_RISK_BY_NAME:
         raise ValueError(f"heads_edl: risk must be one of {', '.join(L.EDL_RISK_BY_NAME)}, got {risk!r}")
-    for name, t, n in (("kl_coef", kl_coef, 1), ("kl_out", kl_out, nh)):
-        if t is not None and (not t.is_cuda or t.dtype != torch.float32 or t.numel() < n or not t.is_contiguous()):
-            raise ValueError(f"heads_edl: {name}: a contiguous float32 device tensor of at least {n} entries")
-    arr = _head_array(heads)
-    dev = labels.device
-    if out is not None:
-        logits, losses, preds, uncertainty, combined = out
-    else:
-        logits = torch.empty(nh, B, K, device=dev)
-        losses = torch.empty(nh + 1, device=dev)
-        preds = torch.empty(nh, B, dtype=torch.int32, device=dev)
-        uncertainty = torch.empty(nh, B, device=dev)
-        combined = torch.empty(B, dtype=torch.int32, device=dev)
+    nh, arr, out = _heads_call("edl", heads, labels, B, K, out, weights, (("kl_coef", kl_coef, 1), ("kl_out", kl_out, len(heads))))
+    logits, losses, preds, uncertainty, combined = out
+    args = (arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(), preds.data_ptr(), uncertainty.data_ptr(),
+            combined.data_ptr(), int(zero_losses), L.ptr(weights))
     if risk is None and kl_coef is None and kl_out is None:
-        L.check(L.lib().m2m_heads_edl(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(), preds.data_ptr(),
-                                      uncertainty.data_ptr(), combined.data_ptr(), int(zero_losses), L.ptr(weights), L.stream_ptr()),
-                "heads_edl")
+        L.check(L.lib().m2m_heads_edl(*args, L.stream_ptr()), "heads_edl")
     else:
-        L.check(L.lib().m2m_heads_edl_risk(arr, nh, labels.data_ptr(), B, D, K, logits.data_ptr(), losses.data_ptr(), preds.data_ptr(),
-                                           uncertainty.data_ptr(), combined.data_ptr(), int(zero_losses), L.ptr(weights),
-                                           L.EDL_RISK_BY_NAME[risk or "mse"], L.ptr(kl_coef), L.ptr(kl_out), L.stream_ptr()),
+        L.check(L.lib().m2m_heads_edl_risk(*args, L.EDL_RISK_BY_NAME[risk or "mse"], L.ptr(kl_coef), L.ptr(kl_out), L.stream_ptr()),
                 "heads_edl_risk")
-    return logits, losses, preds, uncertainty, combined
+    return out
